@@ -14,7 +14,8 @@ counters behind `mfma_busy_pct`, `step_coverage`, the full sub-records -- goes t
 working directory (`--detail-file`) and to stderr.  Inputs are synthetic and resident in HBM before the timed
 region.  The `roofline` object is for the hand-written op with the largest share of the step (mean duration x
 launches), timed live with HIP events on the launch stream.  `cpu_baseline` times the oracle's reference-faithful
-torch-CPU port (oracle/reference_faithful.py) on a bounded sample on the host cores.
+torch-CPU port (oracle/reference_faithful.py) on a bounded sample on the host cores.  `--dump-outputs DIR` also writes
+what the last timed step computed as DIR/<name>.npy (seeded inputs: two builds compare output for output).
 """
 import argparse
 import json
@@ -416,6 +417,60 @@ def emit(full, detail_path):
     print(line, flush=True)
 
 
+DUMP_LIMIT = 64 * 10 ** 6     # --dump-outputs: bytes on disk in all, the .npy headers (128 bytes a file) included
+
+
+def sample_outputs(arrays, limit=DUMP_LIMIT):
+    """name -> array as float32 (float64 stays float64).  Everything is kept whole while it fits `limit`; otherwise every
+    array longer than one common cap is cut to `cap` of its elements, flat indices drawn without replacement by a generator
+    seeded 0 and kept in order: the same elements in every run and every build, the same positions in a parameter and its
+    gradient."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = np.asarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32, order="C")   # (0-d stays 0-d)
+    budget = limit - 128 * len(out)
+
+    def size(cap):
+        return sum(min(a.size, cap) * a.itemsize for a in out.values())
+
+    longest = max((a.size for a in out.values()), default=0)
+    if size(longest) <= budget:
+        return out
+    lo, hi = 0, longest                  # the largest cap that fits
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        lo, hi = (mid, hi) if size(mid) <= budget else (lo, mid - 1)
+    for name, a in out.items():
+        if a.size > lo:
+            out[name] = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, lo, replace=False))]
+    return out
+
+
+def write_outputs(directory, arrays):
+    """`sample_outputs(arrays)` -> directory/<name>.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    kept = sample_outputs(arrays)
+    for name, a in kept.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    print("bench.py: %d arrays, %.1f MB -> %s" % (len(kept), sum(a.nbytes for a in kept.values()) / 1e6, directory),
+          file=sys.stderr, flush=True)
+
+
+def step_outputs(trainer, model, loss, gnorm):
+    """What a training step hands its caller, on the host: the loss and the global gradient norm it returns, every parameter
+    after the Adam update and the (summed) gradient the update used."""
+    grad_of = {id(p): g for p, g in zip(trainer.flat.params, trainer.flat.g_views)}
+    out = {"loss": loss.detach().double().cpu().numpy(), "grad_norm": gnorm.detach().double().cpu().numpy()}
+    for name, p in model.named_parameters():
+        out["param." + name] = p.detach().float().cpu().numpy()
+        if id(p) in grad_of:
+            out["grad." + name] = grad_of[id(p)].float().cpu().numpy()
+    return out
+
+
 def cpu_baseline_worker(batch, threads, budget_s):
     """Runs in a child process (no GPU): CoR2 fwd+bwd of the oracle's reference-faithful torch-CPU port."""
     from oracle import reference_faithful as RF
@@ -577,7 +632,7 @@ def bench_oda_attention(args, world, rank, dev, ops):
         logits = ops.object_difference_attention(vl, ql, w, bias, 0.5, seed)
         alpha, pooled = ops.softmax_attention_pool(logits, v)
         torch.autograd.backward([pooled], [g_pooled])
-        return alpha
+        return alpha, pooled
 
     for i in range(args.warmup):
         step(1000 + i)
@@ -587,11 +642,16 @@ def bench_oda_attention(args, world, rank, dev, ops):
     timer = ops.KernelTimer()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        alpha = step(2000 + i)
+        alpha, pooled = step(2000 + i)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:     # the last timed step's outputs and gradients, before the per-kernel pass reruns it
+        vl, ql = sets[(2000 + args.steps - 1) % len(sets)][:2]
+        write_outputs(args.dump_outputs, {name: t.detach().float().cpu().numpy() for name, t in (
+            ("alpha", alpha), ("pooled", pooled), ("grad.v_low", vl.grad), ("grad.q_low", ql.grad), ("grad.filter", w.grad),
+            ("grad.bias", bias.grad))})
     ops.set_kernel_timer(timer)
     for i in range(min(args.steps, 10)):       # per-kernel durations from a second pass (event pairs around each launch)
         torch.cuda._sleep(24_000_000)
@@ -663,7 +723,13 @@ def main():
                     "(roofline_all, counters, step coverage, full sub-records) is written; stdout carries the compact line only")
     ap.add_argument("--no-sub-records", action="store_true", help="headline only: do not attach the other single-GPU "
                     "BASELINE configs (ODA, the ODA attention op, CoR2 pairwise, CoR2 bf16 N=100) as sub-records")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32; "
+                    "float64 scalars): loss, grad_norm, param.<name> after the update and grad.<name> (the ODA attention op: "
+                    "alpha, pooled, the input and filter gradients); at most 64 MB in all, larger tensors as a fixed seeded "
+                    "sample of their elements (sample_outputs).  Same arguments, same inputs: two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1: the timed region is exactly that many steps")
     os.environ["VQA_F32_PRODUCTS"] = args.f32_products     # (read per call by ops.split_products; children inherit it)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -784,7 +850,9 @@ def main():
         log("timed region done: %.3f s" % elapsed)
         out = {"trainer": trainer, "model": model, "batches": batches, "graphed": graphed, "timer": timer, "warm": warm,
                "elapsed": max_over_ranks(elapsed), "elapsed_local": elapsed, "overlap": bool(trainer.overlap),
-               "final_loss": float(loss.item()), "final_gnorm": float(gnorm.item()), "resident": None}
+               "final_loss": float(loss.item()), "final_gnorm": float(gnorm.item()), "resident": None,
+               # (taken before any further step runs on this trainer: the resident pass below updates the same weights)
+               "outputs": step_outputs(trainer, model, loss, gnorm) if args.dump_outputs and rank == 0 else None}
         # the same steps on ONE resident batch (no copy, inputs from the Infinity Cache): what rounds 1-4 reported as `value`
         if rotate:
             for _ in range(2):
@@ -825,6 +893,8 @@ def main():
             break
     done = [r for r in runs if "elapsed" in r]
     best = min(done, key=lambda r: r["elapsed"])
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, best["outputs"])
     live = done[-1]                 # (the schedule whose trainer is still alive: the per-kernel pass below runs on it)
     trainer, batches, graphed, timer = live["trainer"], live["batches"], live["graphed"], live["timer"]
     (sample, a), v = batches[0], batches[0][0]["v"]

@@ -1,15 +1,15 @@
 #!/usr/bin/env python3
 """Generate the golden fixtures in this directory FROM THE REFERENCE ITSELF.
 
-Runs only in the authoring container (needs /root/reference).  It imports the
+Needs a checkout of the reference (``--reference DIR``).  It imports the
 reference's ``config/CoR2.py`` / ``config/ODA.py`` / ``putils`` with the missing
 third-party packages mocked, swaps the question encoder for an
 identity so the 2400-d question vector is an input, overwrites every parameter
 from ``oracle.seeded`` and records OUTPUTS only (inputs/params are regenerated
 from seeds by the tests).  Nothing of the reference's source text is stored.
 
-    python tests/golden/make_golden.py            # rewrites tests/golden/*.npz
-    python tests/golden/make_golden.py --out /tmp/g --only blocks,encoder   # elsewhere / a subset
+    python tests/golden/make_golden.py --reference DIR            # rewrites tests/golden/*.npz
+    python tests/golden/make_golden.py --reference DIR --out OUT --only blocks,encoder   # elsewhere / a subset
 """
 import contextlib
 import importlib
@@ -26,13 +26,11 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 from oracle import seeded  # noqa: E402
 
-REF = "/root/reference"
-
 
 def _load_by_path(name, path):
     """Import one of the reference's files under a private module name.  The repo has its own ``config`` package (the
     drop-in modules), so ``import config.CoR2`` would resolve to the REPO's model; the reference's files are therefore
-    loaded by path (their own ``from putils import *`` still resolves through sys.path to /root/reference/putils)."""
+    loaded by path (their own ``from putils import *`` still resolves through sys.path to the reference's putils)."""
     import importlib.util
     spec = importlib.util.spec_from_file_location(name, path)
     mod = importlib.util.module_from_spec(spec)
@@ -41,7 +39,8 @@ def _load_by_path(name, path):
     return mod
 
 
-def import_reference():
+def import_reference(path):
+    REF = os.path.realpath(path)
     if REF not in sys.path:
         sys.path.insert(0, REF)
     sys.dont_write_bytecode = True
@@ -270,6 +269,7 @@ def encoder(putils, out_dir=HERE):
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser()
+    ap.add_argument("--reference", required=True, help="root of a checkout of the reference (config/, putils/)")
     ap.add_argument("--out", default=HERE, help="directory the .npz files are written to (default: this directory)")
     ap.add_argument("--only", default="", help="comma list out of blocks,encoder,cor2,oda (default: all)")
     args = ap.parse_args(argv)
@@ -277,7 +277,7 @@ def main(argv=None):
     os.makedirs(args.out, exist_ok=True)
     torch.manual_seed(0)
     torch.set_num_threads(8)
-    cor, oda, putils = import_reference()
+    cor, oda, putils = import_reference(args.reference)
     if not only or "blocks" in only:
         blocks(cor, oda, putils, args.out)
     if not only or "encoder" in only:

@@ -208,3 +208,42 @@ def test_committed_counter_tables_describe_this_tree():
             report.append("%s: %d of %d rows stale" % (os.path.basename(path), len(stale), len(table) - 1))
     if report:
         pytest.skip("counter tables older than the kernels they name (bench.py reports traffic_stale): " + "; ".join(report))
+
+
+def test_dumped_outputs_fit_the_limit_and_sample_the_same_elements(tmp_path):
+    """--dump-outputs: arrays are kept whole while they fit; beyond the limit the long ones are cut to one common cap by a
+    fixed seeded sample (the same elements in every call, the same positions in a parameter and its gradient), the short
+    ones stay whole, and what lands on disk stays under the limit."""
+    import numpy as np
+    rng = np.random.default_rng(5)
+    arrays = {"loss": np.float64(970.125), "grad_norm": np.array(3.25, np.float64),
+              "param.w": np.arange(310 * 2048, dtype=np.float32).reshape(310, 2048),     # (each element its flat index)
+              "param.b": rng.standard_normal(310).astype(np.float32),
+              "grad.w": rng.standard_normal((310, 2048)).astype(np.float32), "grad.b": rng.standard_normal(310).astype(np.float32)}
+    whole = bench.sample_outputs(arrays)
+    assert whole["loss"].dtype == np.float64 and whole["loss"].shape == () and float(whole["loss"]) == 970.125
+    assert whole["param.b"].dtype == np.float32 and whole["param.w"].shape == (310, 2048)
+    assert np.array_equal(whole["grad.w"], arrays["grad.w"])
+
+    limit = 1_000_000
+    cut = bench.sample_outputs(arrays, limit=limit)
+    assert sum(a.nbytes for a in cut.values()) + 128 * len(cut) <= limit
+    assert cut["param.w"].size == cut["grad.w"].size < 310 * 2048 and cut["param.b"].shape == (310,)
+    again = bench.sample_outputs(arrays, limit=limit)
+    assert all(np.array_equal(cut[k], again[k]) for k in cut)
+    pos = cut["param.w"].astype(np.int64)
+    assert np.all(np.diff(pos) > 0) and np.array_equal(arrays["grad.w"].reshape(-1)[pos], cut["grad.w"])
+
+    bench.write_outputs(str(tmp_path / "out"), arrays)
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == sorted(k + ".npy" for k in arrays)
+    assert sum(os.path.getsize(tmp_path / "out" / f) for f in files) <= bench.DUMP_LIMIT
+    assert np.array_equal(np.load(tmp_path / "out" / "param.w.npy"), arrays["param.w"])
+
+
+def test_bench_refuses_an_empty_timed_region():
+    """--steps is the number of timed steps; fewer than one is refused before anything is measured."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr and "{" not in r.stdout
