@@ -9,7 +9,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VQA_LIB_PATH", os.path.join(_HERE, "libvqa_mi355x.so"))  # env override: profiling builds
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _c_f = ctypes.c_void_p          # device pointer to fp32
 _c_pp = ctypes.c_void_p         # host array of device pointers
@@ -151,6 +151,11 @@ SIGNATURES = {
     "vqa_column_sum_bf16": (_c_i, [_c_f, _c_i, _c_f, _c_f, _c_sz, _c_i, _c_i, _c_st]),
     "vqa_kld_sum_loss_workspace_bytes": (_c_sz, [_c_i]),
     "vqa_kld_sum_loss": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_sz, _c_i, _c_i, _c_st]),
+    "vqa_kld_sum_loss_hits_workspace_bytes": (_c_sz, [_c_i, _c_i]),
+    "vqa_kld_sum_loss_hits": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_f, _c_sz, _c_i, _c_i, _c_st]),
+    "vqa_predict_topk_workspace_bytes": (_c_sz, [_c_i, _c_i]),
+    "vqa_predict_topk": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_f, _c_sz, _c_i, _c_i, _c_st]),
+    "vqa_predict_candidates": (_c_i, [_c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_st]),
     "vqa_grad_norm_workspace_bytes": (_c_sz, []),
     "vqa_grad_norm_clip_coef": (_c_i, [_c_f, _c_sz, _c_fl, _c_f, _c_f, _c_sz, _c_st]),
     "vqa_adam_step": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_sz, _c_f, _c_fl, _c_fl, _c_fl, _c_fl, _c_i, _c_st]),

@@ -33,8 +33,11 @@ def soft_target(a_10_idx, num_ans, out=None):
     return a
 
 
+MC_CANDIDATES = 50
+
+
 def collate(items, num_ans, pin=False):
-    """List of reference-style items {'v' [36,2048], 'q_idxes' [T], 'q_id', 'a_10_idx' or 'a'} -> one batch dict of
+    """List of reference-style items {'v' [36,2048], 'q_idxes' [T], 'q_id', 'a_10_idx' or 'a', optionally 'a_mc_idx'} -> one batch dict of
     contiguous host tensors (optionally pinned), the layout Model.forward and the trainer expect."""
     B = len(items)
     v0 = torch.as_tensor(items[0]["v"])
@@ -45,6 +48,14 @@ def collate(items, num_ans, pin=False):
     has_a = "a" in items[0] or "a_10_idx" in items[0]
     if has_a:
         batch["a"] = mk(B, num_ans, dtype=torch.float32)
+    if "a_mc_idx" in items[0]:
+        # MultipleChoice candidates, padded with -1 to MC_CANDIDATES per question (datasets.py:948)
+        batch["a_mc_idx"] = torch.full((B, MC_CANDIDATES), -1, dtype=torch.long)
+        for i, it in enumerate(items):
+            mc = torch.as_tensor(it["a_mc_idx"], dtype=torch.long).reshape(-1)
+            if mc.numel() > MC_CANDIDATES:
+                raise ValueError("item %d has %d multiple-choice candidates, more than %d" % (i, mc.numel(), MC_CANDIDATES))
+            batch["a_mc_idx"][i, :mc.numel()] = mc
     for i, it in enumerate(items):
         batch["v"][i].copy_(torch.as_tensor(it["v"], dtype=torch.float32))
         batch["q_idxes"][i].copy_(torch.as_tensor(it["q_idxes"], dtype=torch.long))

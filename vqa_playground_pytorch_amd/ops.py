@@ -1792,6 +1792,70 @@ def kld_sum_loss(logits, target):
     return KldSumLoss.apply(logits, target)
 
 
+def _check_k(what, C, k):
+    if not 1 <= k <= min(16, C):
+        raise ValueError("%s: k=%d outside [1, min(16, C=%d)]" % (what, k, C))
+
+
+def kld_sum_loss_and_grad_hits(logits, target, kmax):
+    """kld_sum_loss_and_grad plus the target's top-k hits from the same pass over the logits: (loss, d_logits, hits) with
+    hits int32[kmax], hits[j] = rows whose target (first index of the row's largest target value) ranks <= j among the
+    logits.  loss and d_logits are bitwise those of kld_sum_loss_and_grad."""
+    lg, target = _prep("logits", logits.detach()), _prep("target", target)
+    if lg.dim() != 2 or target.shape != lg.shape:
+        raise ValueError("kld_sum_loss: logits and target must both be [B,C], got %s and %s" % (tuple(lg.shape), tuple(target.shape)))
+    B, C = lg.shape
+    kmax = int(kmax)
+    _check_k("kld_sum_loss_hits", C, kmax)
+    loss = torch.empty((), device=lg.device, dtype=torch.float32)
+    d_logits = torch.empty_like(lg)
+    hits = torch.empty(kmax, device=lg.device, dtype=torch.int32)
+    nbytes = _lib.lib().vqa_kld_sum_loss_hits_workspace_bytes(B, kmax)
+    ws = torch.empty(nbytes // 4, device=lg.device, dtype=torch.float32)
+    _launch("kld_sum_loss_hits", (B, C, kmax), _lib.lib().vqa_kld_sum_loss_hits, _p(lg), _p(target), _p(loss), _p(d_logits),
+            _p(hits), kmax, _p(ws), nbytes, B, C)
+    return loss, d_logits, hits
+
+
+def predict_topk(logits, k, target=None, probs=True):
+    """The k best columns of every row in order (int64 [B,k]; column 0 = argmax), the softmax over the whole row at those
+    columns ([B,k], or None with probs=False) and, with a target [B,C], its top-j hits (int32 [k]; else None)."""
+    lg = _prep("logits", logits.detach())
+    if lg.dim() != 2:
+        raise ValueError("predict_topk: logits must be [B,C], got %s" % (tuple(lg.shape),))
+    B, C = lg.shape
+    k = int(k)
+    _check_k("predict_topk", C, k)
+    top_idx = torch.empty(B, k, device=lg.device, dtype=torch.int64)
+    top_prob = torch.empty(B, k, device=lg.device, dtype=torch.float32) if probs else None
+    hits, ws, nbytes = None, None, 0
+    if target is not None:
+        target = _prep("target", target)
+        if target.shape != lg.shape:
+            raise ValueError("predict_topk: target must be [B,C] like the logits, got %s" % (tuple(target.shape),))
+        hits = torch.empty(k, device=lg.device, dtype=torch.int32)
+        nbytes = _lib.lib().vqa_predict_topk_workspace_bytes(B, k)
+        ws = torch.empty(nbytes // 4, device=lg.device, dtype=torch.int32)
+    _launch("predict_topk", (B, C, k), _lib.lib().vqa_predict_topk, _p(lg), _p(target), _p(top_idx), _p(top_prob), _p(hits), k,
+            _p(ws), nbytes, B, C)
+    return top_idx, top_prob, hits
+
+
+def predict_candidates(logits, cand):
+    """int64 [B]: per row, the column among cand[b] (int64 [B,M], entries outside [0, C) ignored) with the best logit
+    (ties to the lower column); -1 for a row without a valid candidate."""
+    lg = _prep("logits", logits.detach())
+    cand = _prep("cand", cand, (torch.int64,))
+    if lg.dim() != 2 or cand.dim() != 2 or cand.size(0) != lg.size(0):
+        raise ValueError("predict_candidates: logits [B,C] and cand [B,M] expected, got %s and %s"
+                         % (tuple(lg.shape), tuple(cand.shape)))
+    B, C = lg.shape
+    M = cand.size(1)
+    pred = torch.empty(B, device=lg.device, dtype=torch.int64)
+    _launch("predict_candidates", (B, C, M), _lib.lib().vqa_predict_candidates, _p(lg), _p(cand), _p(pred), B, C, M)
+    return pred
+
+
 def grad_norm_clip_coef(g_flat, max_norm, out, workspace):
     """out[0] = ||g_flat||_2, out[1] = min(1, max_norm/(norm+1e-6)) -- clip_grad_norm_ semantics (train.py:82)."""
     g_flat = _prep("g_flat", g_flat)

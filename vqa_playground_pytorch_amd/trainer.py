@@ -209,8 +209,16 @@ class DataParallelTrainer:
     EAGER_STEPS_BEFORE_CAPTURE = 2
 
     def __init__(self, model, lr=1e-4, clip=0.25, gamma=0.5 ** (1 / 50000), broadcast=True, group=None,
-                 fused_adam=None, graph=False, adopt_inputs=False, overlap=None, input_slots=1):
+                 fused_adam=None, graph=False, adopt_inputs=False, overlap=None, input_slots=1, topk=None):
         self.model = model
+        # topk=(1, 5): the loss of every step also counts the target's top-k hits (the reference's accuracy(), train.py:22-38,
+        # :70-72) from the same pass over the logits (ops.kld_sum_loss_and_grad_hits); last_hits / last_logits / accuracy()
+        # expose them.  None (the default) issues exactly the launches and captures exactly the graph nodes it did before.
+        self.topk = tuple(int(k) for k in topk) if topk else None
+        if self.topk and not all(1 <= k <= 16 for k in self.topk):
+            raise ValueError("topk=%s: every k must lie in [1, 16] (and not exceed the number of answers)" % (topk,))
+        self.kmax = max(self.topk) if self.topk else 0
+        self._front_out = (None, None, 0)    # (hits, logits, local batch) of the last step's loss launch
         self.group = group
         self.clip = clip
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
@@ -343,12 +351,59 @@ class DataParallelTrainer:
             return self._graph_step(sample, target)
         return self.step_eager(sample, target)
 
+    # ---- top-k hits of the step (topk=...) --------------------------------------------------------------------------
+    @property
+    def last_hits(self):
+        """int32 [kmax] of THIS rank's shard of the last step: hits[j] = rows whose target ranks <= j among the logits (None
+        without topk).  After a replay it is the replayed graph's own output tensor (one per input slot), overwritten by that
+        slot's next replay -- like the loss step() returns."""
+        return self._front_out[0]
+
+    @property
+    def last_logits(self):
+        """The logits [B,C] of the last step on this rank (with topk; None otherwise), under the same lifetime rule."""
+        return self._front_out[1]
+
+    def accuracy(self):
+        """(Acc@k for k in topk), in percent, of the last step over the GLOBAL batch.  Synchronises with the device (the
+        counts are read back), and with more than one rank it all-reduces the hit counts and the batch size -- a
+        collective: every rank must call it.  step() itself never does either."""
+        if not self.topk:
+            raise RuntimeError("accuracy() needs a trainer created with topk=(...)")
+        from . import metrics
+        hits, _, batch = self._front_out
+        if hits is None:
+            raise RuntimeError("accuracy() before the first step")
+        counts = torch.cat([hits.to(torch.int64), torch.tensor([batch], dtype=torch.int64, device=hits.device)])
+        if self.world > 1:
+            dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
+        counts = counts.cpu()
+        return tuple(metrics.accuracy(counts[:-1], int(counts[-1]), self.topk))
+
+    def _loss_and_grad(self, logits, target):
+        """(loss, dL/dlogits) of the fused KLD kernel -- with topk, its variant that also counts the hits."""
+        from . import ops
+        if self.topk:
+            loss, d_logits, hits = ops.kld_sum_loss_and_grad_hits(logits, target, self.kmax)
+            self._front_out = (hits, logits.detach(), logits.size(0))
+            return loss, d_logits
+        return ops.kld_sum_loss_and_grad(logits, target)
+
     def step_eager(self, sample, target):
         """The same step launched kernel by kernel (no graph replay)."""
         if self.overlap:
             return self._step_split_eager(sample, target)
         logits = self.model(sample)
-        loss = kld_sum_loss(logits, target)
+        if self.topk and self.hip:
+            # the gradient the loss node's backward would return (d_logits * 1) without the multiply: bitwise the same
+            loss, d_logits = self._loss_and_grad(logits, target)
+            backward = lambda: torch.autograd.backward(logits, d_logits)   # noqa: E731
+        else:
+            loss = kld_sum_loss(logits, target)
+            backward = loss.backward
+            if self.topk:
+                from . import metrics
+                self._front_out = (metrics.topk_hits(logits, target, self.kmax), logits.detach(), logits.size(0))
         # scheduler.step() precedes optimizer.step() in the reference (train.py:75-86): step t uses lr0*gamma^t
         self.iteration += 1
         self.adam_steps += 1
@@ -358,7 +413,7 @@ class DataParallelTrainer:
             f = self.flat
             f.begin_backward()
             try:
-                loss.backward()
+                backward()
             finally:
                 f.end_backward()
             f.gather_grads()
@@ -370,7 +425,7 @@ class DataParallelTrainer:
         for gp in self.optimizer.param_groups:
             gp["lr"] = lr
         self.grads.zero()
-        loss.backward()
+        backward()
         self.grads.all_reduce_sum(self.group)
         norm = self.grads.clip_(self.clip) if self.clip else None
         self.optimizer.step()
@@ -385,7 +440,7 @@ class DataParallelTrainer:
         ops.begin_step_salts()
         try:
             logits = self.model(sample)
-            loss, d_logits = ops.kld_sum_loss_and_grad(logits, target)     # (loss and its gradient from one kernel)
+            loss, d_logits = self._loss_and_grad(logits, target)     # (loss and its gradient from one kernel)
         finally:
             ops.set_device_seed(None)
         f.begin_backward()
@@ -482,6 +537,7 @@ class DataParallelTrainer:
                 g["target"].copy_(target, non_blocking=True)
         self._set_step_scalars()
         slot["front"].replay()
+        self._front_out = slot["out"]
         if self.reduce:
             dist.all_reduce(f.g, op=dist.ReduceOp.SUM, group=self.group)
         g["tail"].replay()
@@ -503,6 +559,7 @@ class DataParallelTrainer:
         if not self.adopt_inputs:
             target = target.clone()
         split = len(names) == 2
+        eager_out = self._front_out         # the step that ran just before the capture stays "the last step"
         # torch's capture recipe: one forward+backward on a side stream first, so the parameters' AccumulateGrad
         # nodes belong to a capturable stream (nodes created on the default stream would run there and abort the
         # capture).  It only refills the gradient buffer; no parameter is updated.
@@ -534,8 +591,9 @@ class DataParallelTrainer:
         else:
             with torch.cuda.graph(graphs["front"], pool=pool, capture_error_mode=mode):
                 loss = self._front(static_sample, target)
+        captured_out, self._front_out = self._front_out, eager_out
         self._audit_and_instantiate(graphs)
-        return dict(graphs, loss=loss, sample=static_sample, target=target, mode=mode)
+        return dict(graphs, loss=loss, out=captured_out, sample=static_sample, target=target, mode=mode)
 
     def _audit_and_instantiate(self, graphs):
         # Audit before instantiating: a memset node (hipMemsetAsync under capture) is replayed correctly once and then
@@ -574,7 +632,7 @@ class DataParallelTrainer:
             ops.begin_step_salts()
         try:
             logits, outs, ins = self.model.forward_with_cut(sample)
-            loss, d_logits = ops.kld_sum_loss_and_grad(logits, target)
+            loss, d_logits = self._loss_and_grad(logits, target)
         finally:
             if device_seed:
                 ops.set_device_seed(None)
@@ -681,6 +739,7 @@ class DataParallelTrainer:
                 g["target"].copy_(target, non_blocking=True)
         self._set_step_scalars()
         slot["front_a"].replay()
+        self._front_out = slot["out"]
         pending = self._reduce_late_async()
         slot["front_b"].replay()
         self._reduce_early(pending)
