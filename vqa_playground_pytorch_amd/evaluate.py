@@ -92,12 +92,9 @@ class Evaluator:
                 try:
                     self._capture(inputs)
                 except Exception as e:            # noqa: BLE001 -- any capture failure: keep evaluating kernel by kernel
-                    import sys
-                    print("[vqa evaluator] hipGraph capture failed (%s: %s); continuing with eager launches"
-                          % (type(e).__name__, str(e).splitlines()[0] if str(e) else ""), file=sys.stderr)
-                    self._graph = None
+                    from .trainer import report_capture_failure
                     self.want_graph = False
-                    torch.cuda.synchronize()
+                    report_capture_failure("evaluator", e, "continuing with eager launches")
             return out
         g = self._graph
         if not self._matches(inputs):
@@ -108,7 +105,7 @@ class Evaluator:
         return g["out"]
 
     def _capture(self, inputs):
-        from .trainer import graph_node_types
+        from .trainer import audit_and_instantiate
         static = {k: v.clone() for k, v in inputs.items()}
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -119,15 +116,7 @@ class Evaluator:
         graph = torch.cuda.CUDAGraph(keep_graph=True)
         with torch.cuda.graph(graph, pool=torch.cuda.graph_pool_handle()):
             out = self._pass(static)
-        # the trainer's audit: a memset node replays wrongly on this ROCm, and unknown is not clean
-        self.graph_nodes = graph_node_types(graph)
-        if "kernel" not in self.graph_nodes:
-            raise RuntimeError("cannot audit the captured graph for memset nodes (hipGraphGetNodes unavailable)")
-        if self.graph_nodes.get("memset", 0):
-            raise RuntimeError("captured evaluation holds %d memset node(s), which do not replay reliably"
-                               % self.graph_nodes["memset"])
-        graph.instantiate()
-        torch.cuda.synchronize()
+        self.graph_nodes = audit_and_instantiate({"graph": graph}, "evaluation")["graph"]
         self._graph = {"graph": graph, "inputs": static, "out": out}
 
     def run(self, batches, a_vocab=None, eval_metric="OpenEnded", max_step=None):

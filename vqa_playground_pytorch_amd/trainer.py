@@ -56,6 +56,34 @@ def graph_node_types(graph):
         return {}
 
 
+def audit_and_instantiate(graphs, what):
+    """Instantiate the captured graphs {name: CUDAGraph} of `what` (named in the errors) -> {name: node counts}.
+
+    Audit before instantiating: a memset node (hipMemsetAsync under capture) is replayed correctly once and then writes
+    garbage on ROCm 7.2 (tools/graph_memset_check.py).  The library and the models issue none -- zero fills are kernels,
+    the loss and the bias gradients avoid torch's semaphore-based reductions -- and a graph that contains one anyway (a
+    user-supplied seq2vec, a new torch op) must not be replayed."""
+    nodes = {k: graph_node_types(v) for k, v in graphs.items()}
+    if any("kernel" not in c for c in nodes.values()):
+        # the audit could not read the graphs (runtime library not queryable): unknown is not "clean" -- stay eager
+        raise RuntimeError("cannot audit the captured %s for memset nodes (hipGraphGetNodes unavailable)" % what)
+    memsets = sum(c.get("memset", 0) for c in nodes.values())
+    if memsets:
+        raise RuntimeError("captured %s holds %d memset node(s), which do not replay reliably" % (what, memsets))
+    for v in graphs.values():
+        v.instantiate()
+    torch.cuda.synchronize()
+    return nodes
+
+
+def report_capture_failure(who, error, then):
+    """A failed capture is survived (`then` says how); say so once on stderr and let the device drain the attempt."""
+    import sys
+    print("[vqa %s] hipGraph capture failed (%s: %s); %s" % (
+        who, type(error).__name__, str(error).splitlines()[0] if str(error) else "", then), file=sys.stderr)
+    torch.cuda.synchronize()
+
+
 class FlatGradients:
     """One contiguous fp32 buffer holding every parameter's gradient (views installed as p.grad)."""
 
@@ -262,6 +290,7 @@ class DataParallelTrainer:
         self.input_slots = max(1, int(input_slots)) if self.adopt_inputs else 1
         self._slots = []
         self._graph = None
+        self.graph_nodes = {}
         self._eager_steps = 0
         # overlap (GPU path, models that offer late_parameters() / forward_with_cut(): CoR2, ODA): backward runs in two halves;
         # the gradients of the second reasoning step -- complete after the first half -- are all-reduced while the second
@@ -291,6 +320,10 @@ class DataParallelTrainer:
                     split = min(self.flat.offset_of(p) for p in early)
                     if all(self.flat.offset_of(p) + p.numel() <= split for p in late):
                         self.overlap, self._late, self._early, self._split = True, late, early, split
+            # the backward phases of a step (_run_phases), each with the gradient bucket it completes: the whole backward
+            # and the whole buffer, or the two halves with the late bucket (a prefix of the buffer) and the rest
+            g = self.flat.g
+            self._phases = (("front_a", g[:self._split]), ("front_b", g[self._split:])) if self.overlap else (("front", g),)
             # say once which reduction schedule is in effect -- also when the split was asked for and could not be had
             # (the model offers no cut, or a stack group mixes late and early parameters so the late bucket is not a prefix)
             if self.overlap:
@@ -389,60 +422,79 @@ class DataParallelTrainer:
             return loss, d_logits
         return ops.kld_sum_loss_and_grad(logits, target)
 
-    def step_eager(self, sample, target):
-        """The same step launched kernel by kernel (no graph replay)."""
-        if self.overlap:
-            return self._step_split_eager(sample, target)
-        logits = self.model(sample)
-        if self.topk and self.hip:
-            # the gradient the loss node's backward would return (d_logits * 1) without the multiply: bitwise the same
-            loss, d_logits = self._loss_and_grad(logits, target)
-            backward = lambda: torch.autograd.backward(logits, d_logits)   # noqa: E731
-        else:
-            loss = kld_sum_loss(logits, target)
-            backward = loss.backward
-            if self.topk:
-                from . import metrics
-                self._front_out = (metrics.topk_hits(logits, target, self.kmax), logits.detach(), logits.size(0))
-        # scheduler.step() precedes optimizer.step() in the reference (train.py:75-86): step t uses lr0*gamma^t
+    def _advance_lr(self):
+        """scheduler.step() precedes optimizer.step() in the reference (train.py:75-86): step t uses lr0*gamma^t."""
         self.iteration += 1
         self.adam_steps += 1
-        self._lr = lr = self.base_lr * self.gamma ** self.iteration
+        self._lr = self.base_lr * self.gamma ** self.iteration
+        return self._lr
+
+    def step_eager(self, sample, target):
+        """The same step launched kernel by kernel (no graph replay)."""
         if self.hip:
             from . import ops
             f = self.flat
-            f.begin_backward()
-            try:
-                backward()
-            finally:
-                f.end_backward()
-            f.gather_grads()
-            if self.reduce:
-                dist.all_reduce(f.g, op=dist.ReduceOp.SUM, group=self.group)
+            loss = self._run_phases(sample, target, device_seed=False)
+            lr = self._advance_lr()
             ops.grad_norm_clip_coef(f.g, self.clip if self.clip else 0.0, f.norm_and_coef, f.workspace)
             ops.adam_step(f.p, f.g, f.m, f.v, f.norm_and_coef, lr, self.betas[0], self.betas[1], self.eps, self.adam_steps)
-            return loss.detach(), f.norm_and_coef[0]
+            return loss, f.norm_and_coef[0]
+        logits = self.model(sample)
+        loss = kld_sum_loss(logits, target)
+        if self.topk:
+            from . import metrics
+            self._front_out = (metrics.topk_hits(logits, target, self.kmax), logits.detach(), logits.size(0))
         for gp in self.optimizer.param_groups:
-            gp["lr"] = lr
+            gp["lr"] = self._advance_lr()
         self.grads.zero()
-        backward()
+        loss.backward()
         self.grads.all_reduce_sum(self.group)
         norm = self.grads.clip_(self.clip) if self.clip else None
         self.optimizer.step()
         return loss.detach(), norm
 
-    # ---- hipGraph replay of the step ---------------------------------------------------------------------------
-    def _front(self, sample, target):
-        """forward + loss + backward + gradient gather (graph 1)."""
+    # ---- the GPU step: backward phases, each followed by the all-reduce of its gradient bucket -----------------------
+    def _run_phases(self, sample=None, target=None, device_seed=True, slot=None):
+        """The phases of self._phases in order, launched kernel by kernel or, given a captured input slot, replayed from
+        slot[name].  After each phase but the last its bucket's sum-all-reduce is launched asynchronously (it runs under
+        the next phase); the last bucket is reduced synchronously, then the pending reductions are waited for.  Nothing
+        is reduced on a single rank.  -> the loss of a launched step (None for a replay)."""
+        loss, pending = None, []
+        for i, (name, bucket) in enumerate(self._phases):
+            last = i == len(self._phases) - 1
+            if slot is not None:
+                slot[name].replay()
+            else:
+                out = self._phase(i, sample, target, device_seed)
+                if i == 0:
+                    loss = out
+            if self.reduce:
+                work = dist.all_reduce(bucket, op=dist.ReduceOp.SUM, group=self.group, async_op=not last)
+                if not last:
+                    pending.append(work)
+        for work in pending:
+            work.wait()
+        return loss
+
+    def _phase(self, i, sample, target, device_seed=True):
+        """Launch phase i kernel by kernel: the first one runs the forward and the loss and returns the loss, a second one
+        resumes the backward where the first stopped."""
+        launch = getattr(self, "_" + self._phases[i][0])
+        return launch(sample, target, device_seed) if i == 0 else launch()
+
+    def _front(self, sample, target, device_seed=True):
+        """forward + loss + backward + gradient gather: the one-phase step (graph 1)."""
         from . import ops
         f = self.flat
-        ops.set_device_seed(self.seed_word)
-        ops.begin_step_salts()
+        if device_seed:
+            ops.set_device_seed(self.seed_word)
+            ops.begin_step_salts()
         try:
             logits = self.model(sample)
             loss, d_logits = self._loss_and_grad(logits, target)     # (loss and its gradient from one kernel)
         finally:
-            ops.set_device_seed(None)
+            if device_seed:
+                ops.set_device_seed(None)
         f.begin_backward()
         try:
             torch.autograd.backward(logits, d_logits)
@@ -459,9 +511,7 @@ class DataParallelTrainer:
         ops.adam_step_dyn(f.p, f.g, f.m, f.v, f.norm_and_coef, self.step_scalars, self.betas[0], self.betas[1], self.eps)
 
     def _set_step_scalars(self):
-        self.iteration += 1
-        self.adam_steps += 1
-        self._lr = lr = self.base_lr * self.gamma ** self.iteration
+        lr = self._advance_lr()
         slot = self.adam_steps % self._ring
         # A replayed step costs the host a few launches per ~3 ms of GPU work, so a loop that never synchronises runs far
         # ahead: without this wait the slot of step t could be rewritten with step t + ring's values before the GPU has
@@ -477,35 +527,29 @@ class DataParallelTrainer:
         done.record()
         self._ring_events[slot] = done
 
+    # ---- hipGraph replay of the step ---------------------------------------------------------------------------
+    def _device_seeded_step(self, sample, target):
+        """A step launched kernel by kernel with the launches, device-side seed and step scalars of a replay -> the loss."""
+        self._set_step_scalars()
+        loss = self._run_phases(sample, target)
+        self._tail()
+        return loss
+
     def _graph_step(self, sample, target):
         from . import ops
         f = self.flat
-        if self.overlap:
-            return self._graph_step_split(sample, target)
-        if self._graph is None:
+        g = self._graph
+        if g is None:
             seeds_before = ops.host_seed_draws
-            self._set_step_scalars()
-            loss = self._front(sample, target)
-            if self.reduce:
-                dist.all_reduce(f.g, op=dist.ReduceOp.SUM, group=self.group)
-            self._tail()
+            loss = self._device_seeded_step(sample, target)
             self._eager_steps += 1
             if ops.host_seed_draws != seeds_before:
                 self.want_graph = False       # host-seeded dropout mask in the forward: replay would freeze it
             elif self._eager_steps >= self.EAGER_STEPS_BEFORE_CAPTURE:   # warmed up (allocator, LDS attributes, GEMM table): capture
-                try:
-                    self._capture(sample, target)
-                except Exception as e:        # noqa: BLE001 -- any capture failure: keep training, kernel by kernel
-                    import sys
-                    print("[vqa trainer] hipGraph capture failed (%s: %s); continuing with eager launches"
-                          % (type(e).__name__, str(e).splitlines()[0] if str(e) else ""), file=sys.stderr)
-                    self._graph = None
-                    self.want_graph = False
-                    torch.cuda.synchronize()
+                self._capture(sample, target)
             return loss, f.norm_and_coef[0]
-        g = self._graph
-        if self.model.training != g["training"] or target.shape != g["target"].shape or any(k not in sample or sample[k].shape != t.shape or sample[k].dtype != t.dtype
-                                                    for k, t in g["sample"].items()):
+        if self.model.training != g["training"] or target.shape != g["target"].shape or any(
+                k not in sample or sample[k].shape != t.shape or sample[k].dtype != t.dtype for k, t in g["sample"].items()):
             # a batch of another shape (the last one of an epoch), or the model switched between train() and eval() since
             # the capture (dropout is baked into the graph): this step is launched kernel by kernel; the captured graphs
             # stay valid for the regular steps that follow
@@ -513,20 +557,9 @@ class DataParallelTrainer:
         slot = self._slot_of(sample, target)
         if slot is None and len(self._slots) < self.input_slots:
             # a slot of the feeder's ring the step has not been captured on yet: this step runs kernel by kernel (the same
-            # launches, device-side seed and step scalars as a replay), then the front graph is captured on the slot's tensors
-            self._set_step_scalars()
-            loss = self._front(sample, target)
-            if self.reduce:
-                dist.all_reduce(f.g, op=dist.ReduceOp.SUM, group=self.group)
-            self._tail()
-            try:
-                self._slots.append(self._capture_front(sample, target, g["pool"], ("front",)))
-            except Exception as e:        # noqa: BLE001 -- keep training: further batches of this slot are copied into slot 0
-                import sys
-                print("[vqa trainer] capture of input slot %d failed (%s: %s); its batches will be copied into slot 0"
-                      % (len(self._slots), type(e).__name__, str(e).splitlines()[0] if str(e) else ""), file=sys.stderr)
-                self.input_slots = len(self._slots)
-                torch.cuda.synchronize()
+            # launches, device-side seed and step scalars as a replay), then the front is captured on the slot's tensors
+            loss = self._device_seeded_step(sample, target)
+            self._capture(sample, target)
             return loss, f.norm_and_coef[0]
         if slot is None:
             slot = g
@@ -536,10 +569,8 @@ class DataParallelTrainer:
             if target.data_ptr() != g["target"].data_ptr():
                 g["target"].copy_(target, non_blocking=True)
         self._set_step_scalars()
-        slot["front"].replay()
         self._front_out = slot["out"]
-        if self.reduce:
-            dist.all_reduce(f.g, op=dist.ReduceOp.SUM, group=self.group)
+        self._run_phases(slot=slot)
         g["tail"].replay()
         return slot["loss"], f.norm_and_coef[0]
 
@@ -551,14 +582,38 @@ class DataParallelTrainer:
                 return slot
         return None
 
-    def _capture_front(self, sample, target, pool, names):
-        """Capture forward + loss + backward + gather (names = ("front",)) or its two halves (("front_a", "front_b")) reading
-        `sample` / `target` -- the caller's tensors with adopt_inputs, private copies otherwise.  -> the slot record."""
+    def _capture(self, sample, target):
+        """Capture the step on this batch: the first time its phases and the tail, in a new memory pool, afterwards the
+        phases once more on the tensors of a new input slot (the graphs share the pool: they never run concurrently).
+        Any failure keeps training: kernel by kernel after a failed first capture, on the slots captured so far after a
+        failed slot capture (further batches of that slot are copied into slot 0)."""
+        first = self._graph is None
+        try:
+            pool = torch.cuda.graph_pool_handle() if first else self._graph["pool"]
+            slot = self._capture_front(sample, target, pool)
+            if first:
+                tail = torch.cuda.CUDAGraph(keep_graph=True)
+                with torch.cuda.graph(tail, pool=pool, capture_error_mode=slot["mode"]):
+                    self._tail()
+                self.graph_nodes.update(audit_and_instantiate({"tail": tail}, "step"))
+                self._graph = dict(slot, tail=tail, pool=pool, training=self.model.training)
+            self._slots.append(slot)
+        except Exception as e:                # noqa: BLE001 -- any capture failure: keep training
+            if first:
+                self.want_graph = False
+                then = "continuing with eager launches"
+            else:
+                self.input_slots = len(self._slots)
+                then = "batches of input slot %d will be copied into slot 0" % len(self._slots)
+            report_capture_failure("trainer", e, then)
+
+    def _capture_front(self, sample, target, pool):
+        """Capture the phases, one graph each, reading `sample` / `target` -- the caller's tensors with adopt_inputs,
+        private copies otherwise.  -> the slot record."""
         static_sample = {k: (v if self.adopt_inputs else v.clone()) for k, v in sample.items()
                          if isinstance(v, torch.Tensor) and k in self._model_keys(sample)}
         if not self.adopt_inputs:
             target = target.clone()
-        split = len(names) == 2
         eager_out = self._front_out         # the step that ran just before the capture stays "the last step"
         # torch's capture recipe: one forward+backward on a side stream first, so the parameters' AccumulateGrad
         # nodes belong to a capturable stream (nodes created on the default stream would run there and abort the
@@ -566,11 +621,8 @@ class DataParallelTrainer:
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            if split:
-                self._front_a(static_sample, target)
-                self._front_b()
-            else:
-                self._front(static_sample, target)
+            for i in range(len(self._phases)):
+                self._phase(i, static_sample, target)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         mode = "global"
@@ -582,46 +634,13 @@ class DataParallelTrainer:
             torch.cuda.synchronize()
             time.sleep(1.0)
             mode = "thread_local"
-        graphs = {k: torch.cuda.CUDAGraph(keep_graph=True) for k in names}
-        if split:
-            with torch.cuda.graph(graphs["front_a"], pool=pool, capture_error_mode=mode):
-                loss = self._front_a(static_sample, target)
-            with torch.cuda.graph(graphs["front_b"], pool=pool, capture_error_mode=mode):
-                self._front_b()
-        else:
-            with torch.cuda.graph(graphs["front"], pool=pool, capture_error_mode=mode):
-                loss = self._front(static_sample, target)
+        graphs, outs = {name: torch.cuda.CUDAGraph(keep_graph=True) for name, _ in self._phases}, []
+        for i, graph in enumerate(graphs.values()):
+            with torch.cuda.graph(graph, pool=pool, capture_error_mode=mode):
+                outs.append(self._phase(i, static_sample, target))
         captured_out, self._front_out = self._front_out, eager_out
-        self._audit_and_instantiate(graphs)
-        return dict(graphs, loss=loss, out=captured_out, sample=static_sample, target=target, mode=mode)
-
-    def _audit_and_instantiate(self, graphs):
-        # Audit before instantiating: a memset node (hipMemsetAsync under capture) is replayed correctly once and then
-        # writes garbage on ROCm 7.2 (tools/graph_memset_check.py).  The library and the model issue none -- zero fills
-        # are kernels, the loss and the bias gradients avoid torch's semaphore-based reductions -- and a step that
-        # contains one anyway (a user-supplied seq2vec, a new torch op) must not be replayed.
-        nodes = {k: graph_node_types(v) for k, v in graphs.items()}
-        self.graph_nodes = dict(getattr(self, "graph_nodes", None) or {}, **nodes)
-        if any("kernel" not in c for c in nodes.values()):
-            # the audit could not read the graphs (runtime library not queryable): unknown is not "clean" -- stay eager
-            raise RuntimeError("cannot audit the captured graphs for memset nodes (hipGraphGetNodes unavailable)")
-        memsets = sum(c.get("memset", 0) for c in nodes.values())
-        if memsets:
-            raise RuntimeError("captured step holds %d memset node(s), which do not replay reliably" % memsets)
-        for v in graphs.values():
-            v.instantiate()
-        torch.cuda.synchronize()
-
-    def _capture(self, sample, target):
-        pool = torch.cuda.graph_pool_handle()
-        self.graph_nodes = {}
-        slot = self._capture_front(sample, target, pool, ("front",))
-        tail = torch.cuda.CUDAGraph(keep_graph=True)
-        with torch.cuda.graph(tail, pool=pool, capture_error_mode=slot["mode"]):
-            self._tail()
-        self._audit_and_instantiate({"tail": tail})
-        self._slots = [slot]
-        self._graph = dict(slot, tail=tail, pool=pool, training=self.model.training)
+        self.graph_nodes.update(audit_and_instantiate(graphs, "step"))
+        return dict(graphs, loss=outs[0], out=captured_out, sample=static_sample, target=target, mode=mode)
 
     # ---- backward in two halves, the first all-reduce under the second (overlap=True) ---------------------------------
     def _front_a(self, sample, target, device_seed=True):
@@ -658,104 +677,6 @@ class DataParallelTrainer:
         finally:
             ops.set_grad_slots(self.flat.p, None)
         self.flat.store_grads(self._early, grads)
-
-    def _reduce_late_async(self):
-        if self.reduce:
-            return dist.all_reduce(self.flat.g[:self._split], op=dist.ReduceOp.SUM, group=self.group, async_op=True)
-        return None
-
-    def _reduce_early(self, pending):
-        if self.reduce:
-            dist.all_reduce(self.flat.g[self._split:], op=dist.ReduceOp.SUM, group=self.group)
-        if pending is not None:
-            pending.wait()
-
-    def _step_split_eager(self, sample, target):
-        from . import ops
-        f = self.flat
-        loss = self._front_a(sample, target, device_seed=False)
-        pending = self._reduce_late_async()
-        self._front_b()
-        self._reduce_early(pending)
-        self.iteration += 1
-        self.adam_steps += 1
-        self._lr = lr = self.base_lr * self.gamma ** self.iteration
-        ops.grad_norm_clip_coef(f.g, self.clip if self.clip else 0.0, f.norm_and_coef, f.workspace)
-        ops.adam_step(f.p, f.g, f.m, f.v, f.norm_and_coef, lr, self.betas[0], self.betas[1], self.eps, self.adam_steps)
-        return loss, f.norm_and_coef[0]
-
-    def _graph_step_split(self, sample, target):
-        from . import ops
-        f = self.flat
-        if self._graph is None:
-            seeds_before = ops.host_seed_draws
-            self._set_step_scalars()
-            loss = self._front_a(sample, target)
-            pending = self._reduce_late_async()
-            self._front_b()
-            self._reduce_early(pending)
-            self._tail()
-            self._eager_steps += 1
-            if ops.host_seed_draws != seeds_before:
-                self.want_graph = False
-            elif self._eager_steps >= self.EAGER_STEPS_BEFORE_CAPTURE:
-                try:
-                    self._capture_split(sample, target)
-                except Exception as e:        # noqa: BLE001 -- any capture failure: keep training, kernel by kernel
-                    import sys
-                    print("[vqa trainer] hipGraph capture failed (%s: %s); continuing with eager launches"
-                          % (type(e).__name__, str(e).splitlines()[0] if str(e) else ""), file=sys.stderr)
-                    self._graph = None
-                    self.want_graph = False
-                    torch.cuda.synchronize()
-            return loss, f.norm_and_coef[0]
-        g = self._graph
-        if self.model.training != g["training"] or target.shape != g["target"].shape or any(
-                k not in sample or sample[k].shape != t.shape or sample[k].dtype != t.dtype for k, t in g["sample"].items()):
-            return self.step_eager(sample, target)
-        slot = self._slot_of(sample, target)
-        if slot is None and len(self._slots) < self.input_slots:      # a new slot of the feeder's ring: see _graph_step
-            self._set_step_scalars()
-            loss = self._front_a(sample, target)
-            pending = self._reduce_late_async()
-            self._front_b()
-            self._reduce_early(pending)
-            self._tail()
-            try:
-                self._slots.append(self._capture_front(sample, target, g["pool"], ("front_a", "front_b")))
-            except Exception as e:        # noqa: BLE001
-                import sys
-                print("[vqa trainer] capture of input slot %d failed (%s: %s); its batches will be copied into slot 0"
-                      % (len(self._slots), type(e).__name__, str(e).splitlines()[0] if str(e) else ""), file=sys.stderr)
-                self.input_slots = len(self._slots)
-                torch.cuda.synchronize()
-            return loss, f.norm_and_coef[0]
-        if slot is None:
-            slot = g
-            for k, t in g["sample"].items():
-                if sample[k].data_ptr() != t.data_ptr():
-                    t.copy_(sample[k], non_blocking=True)
-            if target.data_ptr() != g["target"].data_ptr():
-                g["target"].copy_(target, non_blocking=True)
-        self._set_step_scalars()
-        slot["front_a"].replay()
-        self._front_out = slot["out"]
-        pending = self._reduce_late_async()
-        slot["front_b"].replay()
-        self._reduce_early(pending)
-        g["tail"].replay()
-        return slot["loss"], f.norm_and_coef[0]
-
-    def _capture_split(self, sample, target):
-        pool = torch.cuda.graph_pool_handle()
-        self.graph_nodes = {}
-        slot = self._capture_front(sample, target, pool, ("front_a", "front_b"))
-        tail = torch.cuda.CUDAGraph(keep_graph=True)
-        with torch.cuda.graph(tail, pool=pool, capture_error_mode=slot["mode"]):
-            self._tail()
-        self._audit_and_instantiate({"tail": tail})
-        self._slots = [slot]
-        self._graph = dict(slot, tail=tail, pool=pool, training=self.model.training)
 
     @property
     def lr(self):
