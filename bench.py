@@ -7,10 +7,12 @@ fp32, dropout active -- BASELINE.json configs[1] (N=1) / configs[3] (N=8, global
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 5
 
-Rank 0 prints ONE compact JSON line (< 2000 bytes: `compact_line`) on stdout: the contract fields, `roofline`,
-`cpu_baseline`, `resident_inputs`, one small record per sub-benchmark and, for N > 1, `distributed`.  Everything
-else -- `roofline_all` (EVERY timed op of the step, C-ABI launches and library GEMMs, with its work model), the
-counters behind `mfma_busy_pct`, `step_coverage`, the full sub-records -- goes to `bench_detail.json` in the
+Rank 0 prints ONE compact JSON line (< 2000 bytes: `compact_line`) on stdout: the contract fields, the configuration
+and, for N > 1, `distributed`.  A plain run does only what that line needs: set up, warm up, time the K steps, write
+`--dump-outputs`, print.  `--full` adds everything measured in runs of its own, after the timed region: `roofline`,
+`cpu_baseline`, `resident_inputs` and one small record per sub-benchmark on the line; `roofline_all` (EVERY timed op
+of the step, C-ABI launches and library GEMMs, with its work model), the counters behind `mfma_busy_pct`,
+`step_coverage` and the full sub-records in the full record.  The full record goes to `bench_detail.json` in the
 working directory (`--detail-file`) and to stderr.  Inputs are synthetic and resident in HBM before the timed
 region.  The `roofline` object is for the hand-written op with the largest share of the step (mean duration x
 launches), timed live with HIP events on the launch stream.  `cpu_baseline` times the oracle's reference-faithful
@@ -343,6 +345,52 @@ def step_table(timer, steps_timed, B, regions, bf16, model_name="cor2"):
     return entries
 
 
+def roofline_record(timer, args, B, bf16, graphed, ms_step):
+    """--full, a training step: `roofline`, `traffic_source`, `step_coverage` and `roofline_all` from the per-kernel pass."""
+    steps_timed = min(args.steps, 10) if (graphed or not args.no_graph) else args.steps
+    entries = step_table(timer, steps_timed, B, args.regions, bf16, args.model)
+    # `roofline` = the hand-written OP that takes the largest share of the step -- its launches summed over every shape
+    # it runs at (linear_act_fwd runs once with and once without the in-register dropout mask: two entries of
+    # roofline_all, one op) -- not a favourite; library GEMMs (hipBLASLt through torch) are listed in roofline_all with
+    # their time and rate as well
+    ours = [e for e in entries if e["bound"] is not None and e["kernel"] != "library_gemm"]
+    by_op = {}
+    for e in ours:
+        by_op.setdefault(e["kernel"], []).append(e)
+    dominant = None
+    if by_op:
+        name, group = max(by_op.items(), key=lambda kv: sum(e["ms_per_step"] for e in kv[1]))
+        launches = sum(e["launches"] for e in group)
+        total_ms = sum(e["mean_ms"] * e["launches"] for e in group)
+        work = sum(e["achieved"] * e["mean_ms"] * e["launches"] for e in group)        # (rate x time = work, per entry)
+        lead = max(group, key=lambda e: e["ms_per_step"])
+        dominant = {"bound": lead["bound"], "achieved": round(work / total_ms, 2), "peak": lead["peak"], "unit": lead["unit"],
+                    "frac": round(work / total_ms / lead["peak"], 4),
+                    "traffic": lead["traffic"], "kernel": name, "mean_ms": round(total_ms / launches, 5),
+                    "launches": launches, "ms_per_step": round(sum(e["ms_per_step"] for e in group), 5),
+                    "shapes": [e["shape"] for e in group],
+                    "device_kernels": lead.get("device_kernels", PMC_KERNELS.get(name, []))}
+        for k in ("mfma_busy_pct", "valu_issue_pct_min", "traffic_stale"):
+            if k in lead:
+                dominant[k] = lead[k]
+        if all("trace_ms" in e for e in group):      # the same op in the committed trace of the replayed step, launch-weighted
+            dominant["trace_ms"] = round(sum(e["trace_ms"] * e["launches"] for e in group) / launches, 5)
+    else:
+        dominant = dict(entries[0])
+    kernel_ms = sum(e["ms_per_step"] for e in entries)
+    lib_ms = sum(e["ms_per_step"] for e in entries if e["kernel"] == "library_gemm")
+    return {
+        "roofline": dominant,
+        "traffic_source": "profiles/%s_pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command "
+                          "(committed evidence; no profiler is attached in this run)" % EVIDENCE_TAG,
+        # how much of the step the per-kernel table accounts for (its durations come from the kernel-by-kernel pass,
+        # ms_per_step from the replayed graphs; the rest is framework glue: small element-wise kernels, copies, gaps)
+        "step_coverage": {"timed_ops_ms": round(kernel_ms, 3), "of_ms_per_step": round(kernel_ms / ms_step, 3),
+                          "library_gemm_ms": round(lib_ms, 3), "hand_written_ms": round(kernel_ms - lib_ms, 3)},
+        "roofline_all": entries,
+    }
+
+
 COMPACT_LIMIT = 2000        # bytes: the driver keeps a 2000-character tail of stdout and parses the last line of it
 
 
@@ -351,8 +399,9 @@ def _pick(d, keys):
 
 
 def compact_line(full):
-    """The ONE stdout line: the driver-contract fields + `roofline` + `cpu_baseline` (+ `resident_inputs`, one small record
-    per sub-benchmark, `distributed` for N > 1), built from the full result and kept under COMPACT_LIMIT bytes -- the
+    """The ONE stdout line: the driver-contract fields and the configuration (+ `distributed` for N > 1; with --full also
+    `roofline`, `cpu_baseline`, `resident_inputs` and one small record per sub-benchmark, each when the full result holds
+    it), built from the full result and kept under COMPACT_LIMIT bytes -- the
     record that outgrew the harness in round 3 (21 KB, `parsed: null`) cannot happen again: optional parts are dropped,
     last first, until the line fits (tests/test_bench_line.py)."""
     line = _pick(full, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -362,7 +411,8 @@ def compact_line(full):
     if cfg.get("warmup_run"):
         line["config"]["warmup_run"] = str(cfg["warmup_run"]).split(" (")[0]
     line["config"]["workload"] = str(line["config"].get("workload", ""))[:130]
-    line["roofline"] = _pick(full.get("roofline"), ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "mean_ms",
+    if full.get("roofline") is not None:
+        line["roofline"] = _pick(full["roofline"], ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "mean_ms",
                                                     "launches", "mfma_busy_pct", "valu_issue_pct_min", "traffic_stale", "trace_ms"))
     if full.get("cpu_baseline") is not None:
         cb = full["cpu_baseline"]
@@ -542,8 +592,8 @@ class CpuBaseline:
         return best
 
 
-# The other single-GPU BASELINE configs, attached to the headline line as sub-records (each a child run of this file on the
-# same GPU, after the headline's timed region): SURVEY 8d config 3 (the ODA attention op), the ODA head at batch 512
+# The other single-GPU BASELINE configs, attached to the headline line by --full as sub-records (each a child run of this file
+# on the same GPU, after the headline's timed region): SURVEY 8d config 3 (the ODA attention op), the ODA head at batch 512
 # (configs[2]), the CoR2 step with the relation step's forward on the pairwise kernel, and one rank's share of configs[4].
 SUB_RECORDS = [
     ("oda_b512", ["--model", "oda"]),
@@ -564,7 +614,7 @@ def run_sub_records(steps, warmup, detail_path, timeout_s=150.0):
     for tag, extra in SUB_RECORDS:
         child_detail = "%s_%s.json" % (stem, tag)
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
-               "--no-cpu-baseline", "--no-sub-records", "--detail-file", child_detail] + extra
+               "--full", "--no-cpu-baseline", "--no-sub-records", "--detail-file", child_detail] + extra
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s, cwd=ROOT)
@@ -652,21 +702,20 @@ def bench_oda_attention(args, world, rank, dev, ops):
         write_outputs(args.dump_outputs, {name: t.detach().float().cpu().numpy() for name, t in (
             ("alpha", alpha), ("pooled", pooled), ("grad.v_low", vl.grad), ("grad.q_low", ql.grad), ("grad.filter", w.grad),
             ("grad.bias", bias.grad))})
-    ops.set_kernel_timer(timer)
-    for i in range(min(args.steps, 10)):       # per-kernel durations from a second pass (event pairs around each launch)
-        torch.cuda._sleep(24_000_000)
-        step(3000 + i)
-    torch.cuda.synchronize()
-    ops.set_kernel_timer(None)
+    if args.full:
+        ops.set_kernel_timer(timer)
+        for i in range(min(args.steps, 10)):       # per-kernel durations from a second pass (event pairs around each launch)
+            torch.cuda._sleep(24_000_000)
+            step(3000 + i)
+        torch.cuda.synchronize()
+        ops.set_kernel_timer(None)
     t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     assert torch.isfinite(alpha).all() and torch.isfinite(w.grad).all() and all(torch.isfinite(st[0].grad).all() for st in sets if st[0].grad is not None)
     if rank == 0:
-        entries = step_table(timer, min(args.steps, 10), B, N, False, "oda-attention")
-        dominant = next(e for e in entries if e["bound"] is not None)
-        emit({
+        result = {
             "metric": "ODA object-difference attention op samples/sec (fwd+bwd), batch %d, %dx%d pairwise" % (B, N, N),
             "value": round(world * B * args.steps / elapsed, 1), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True,
@@ -674,10 +723,15 @@ def bench_oda_attention(args, world, rank, dev, ops):
             "config": {"workload": "ODA attention op alone (BASELINE configs[2]; SURVEY 8d config 3): v_low [%d,%d,310], q_low, "
                                    "v [%d,%d,2048], filter (4, %d) -> alpha, pooled; fwd+bwd, dropout 0.5 in K2"
                                    % (B, N, B, N, N * LOW), "global_batch": world * B, "launch": "eager",
-                       "parallelism": "dp%d" % world},
-            "roofline": {k: dominant[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "mean_ms",
-                                                  "launches", "mfma_busy_pct", "valu_issue_pct_min") if k in dominant},
-            "roofline_all": entries}, args.detail_file)
+                       "parallelism": "dp%d" % world}}
+        if args.full:
+            entries = step_table(timer, min(args.steps, 10), B, N, False, "oda-attention")
+            dominant = next(e for e in entries if e["bound"] is not None)
+            result["roofline"] = {k: dominant[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel",
+                                                           "mean_ms", "launches", "mfma_busy_pct", "valu_issue_pct_min")
+                                  if k in dominant}
+            result["roofline_all"] = entries
+        emit(result, args.detail_file)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -690,12 +744,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     # defaults: a timed region of ~0.5 s (200 replayed steps) behind 10 warm-up steps -- long enough for a utilisation sampler
     # and for the clocks to settle (measured: 20, 200 and 1000 timed steps after 10 warm-up steps agree within 0.2 %; after
-    # only 5 the first timed steps still run ~1 % slow); the whole default run, sub-records and CPU baseline included, takes
-    # about 75 s
+    # only 5 the first timed steps still run ~1 % slow); the whole default run with --full, sub-records and CPU baseline
+    # included, takes about 75 s
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true", help="after the timed region, also measure what takes runs of its own: "
+                    "the per-kernel roofline pass, the resident-batch pass, the all-reduce alone (N > 1), the sub-records "
+                    "and the CPU baseline (headline config at N = 1); without it a run only sets up, warms up, times the "
+                    "steps, writes --dump-outputs and prints the line")
     ap.add_argument("--batch", type=int, default=BATCH, help="per-GPU batch (BASELINE config: 512)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--relation-mode", type=int, default=1, help="K1: 0 = pairwise, 1 = factored")
     ap.add_argument("--model", default="cor2", choices=["cor2", "oda", "oda-attention"], help="cor2 = the headline config; "
                     "oda = the ODA head (3000 answers), reported the same way; oda-attention = BASELINE configs[2] / SURVEY "
@@ -720,8 +778,9 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel from the host instead of replaying "
                     "the captured hipGraphs of the step")
     ap.add_argument("--detail-file", default=os.path.join(os.getcwd(), "bench_detail.json"), help="where the full record "
-                    "(roofline_all, counters, step coverage, full sub-records) is written; stdout carries the compact line only")
-    ap.add_argument("--no-sub-records", action="store_true", help="headline only: do not attach the other single-GPU "
+                    "(with --full: roofline_all, counters, step coverage, full sub-records) is written; stdout carries the "
+                    "compact line only")
+    ap.add_argument("--no-sub-records", action="store_true", help="--full: do not attach the other single-GPU "
                     "BASELINE configs (ODA, the ODA attention op, CoR2 pairwise, CoR2 bf16 N=100) as sub-records")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32; "
                     "float64 scalars): loss, grad_norm, param.<name> after the update and grad.<name> (the ODA attention op: "
@@ -839,7 +898,7 @@ def main():
         log("warmup done (graph replay: %s, overlap: %s)" % (graphed, bool(trainer.overlap)))
         timer = ops.KernelTimer()
         barrier()
-        if not graphed and args.no_graph:
+        if not graphed and args.no_graph:     # (with or without --full: the timed steps are the same either way)
             ops.set_kernel_timer(timer)
         t0 = time.perf_counter()
         for i in range(args.steps):
@@ -853,8 +912,9 @@ def main():
                "final_loss": float(loss.item()), "final_gnorm": float(gnorm.item()), "resident": None,
                # (taken before any further step runs on this trainer: the resident pass below updates the same weights)
                "outputs": step_outputs(trainer, model, loss, gnorm) if args.dump_outputs and rank == 0 else None}
-        # the same steps on ONE resident batch (no copy, inputs from the Infinity Cache): what rounds 1-4 reported as `value`
-        if rotate:
+        # --full: the same steps on ONE resident batch (no copy, inputs from the Infinity Cache), what rounds 1-4 reported
+        # as `value`
+        if rotate and args.full:
             for _ in range(2):
                 trainer.step(*batches[0])
             barrier()
@@ -900,7 +960,7 @@ def main():
     (sample, a), v = batches[0], batches[0][0]["v"]
     elapsed, resident = best["elapsed"], best["resident"]
     final_loss, final_gnorm = best["final_loss"], best["final_gnorm"]
-    if graphed or not args.no_graph:
+    if args.full and (graphed or not args.no_graph):
         # HIP events cannot be recorded inside hipGraph replays, so the per-kernel durations for `roofline` are taken
         # live from an identical run of the same steps launched kernel by kernel, right after the timed region.
         # Each of these steps is queued behind a ~10 ms device-side sleep, so the host has enqueued the whole step before
@@ -914,69 +974,53 @@ def main():
         barrier()
         ops.set_kernel_timer(None)
     headline = world == 1 and args.model == "cor2" and not bf16 and args.regions == REGIONS and not args.encoder
-    want_cpu = rank == 0 and headline and not args.no_cpu_baseline
+    want_cpu = rank == 0 and headline and args.full and not args.no_cpu_baseline
     dist_info = None
     if world > 1:
-        # what a reader needs to sanity-check a scaling record: ranks seen by the process group, the all-reduce payload and
-        # its duration measured on its own (back to back, nothing to overlap with), the per-rank rate
+        # what a reader needs to sanity-check a scaling record: ranks seen by the process group, the all-reduce payload, the
+        # per-rank rate and, with --full, the all-reduce's duration measured on its own (back to back, nothing to overlap with)
         payload = trainer.flat.g
-        for _ in range(3):
-            dist.all_reduce(payload, op=dist.ReduceOp.SUM)
-        barrier()
-        a0 = time.perf_counter()
-        for _ in range(10):
-            dist.all_reduce(payload, op=dist.ReduceOp.SUM)
-        barrier()
-        ar_ms = 1e3 * (time.perf_counter() - a0) / 10
-        payload.zero_()
         dist_info = {"nranks": dist.get_world_size(), "backend": dist.get_backend(), "allreduce_payload_bytes": payload.numel() * 4,
-                     "allreduce_ms_alone": round(ar_ms, 3),
-                     "allreduce_busbw_GBs": round(2 * (world - 1) / world * payload.numel() * 4 / (ar_ms * 1e-3) / 1e9, 1),
                      "per_rank_samples_per_s": round(B * args.steps / elapsed, 1), "overlap": bool(best["overlap"]),
                      # both reduction schedules, timed in this invocation (K steps each); `value` is the faster one
                      "schedules": {("overlap" if r["overlap"] else "single"):
                                    ({"value": round(world * B * args.steps / r["elapsed"], 1),
                                      "ms_per_step": round(1e3 * r["elapsed"] / args.steps, 3)} if "elapsed" in r
                                     else {"error": r["failed"]}) for r in runs}}
+        if args.full:
+            for _ in range(3):
+                dist.all_reduce(payload, op=dist.ReduceOp.SUM)
+            barrier()
+            a0 = time.perf_counter()
+            for _ in range(10):
+                dist.all_reduce(payload, op=dist.ReduceOp.SUM)
+            barrier()
+            ar_ms = 1e3 * (time.perf_counter() - a0) / 10
+            payload.zero_()
+            dist_info["allreduce_ms_alone"] = round(ar_ms, 3)
+            dist_info["allreduce_busbw_GBs"] = round(2 * (world - 1) / world * payload.numel() * 4 / (ar_ms * 1e-3) / 1e9, 1)
     # sanity of the timed steps themselves (a replayed graph that computed garbage would still be fast): the loss of
     # the last timed step is finite and positive (a KL divergence) and the gradient norm is of a trainable size
     assert final_loss == final_loss and 0.0 < final_loss < 1e6, "implausible loss %r in the timed region" % final_loss
     assert final_gnorm == final_gnorm and 0.0 < final_gnorm < 1e4, "implausible gradient norm %r" % final_gnorm
 
     if rank == 0:
-        steps_timed = min(args.steps, 10) if (graphed or not args.no_graph) else args.steps
-        entries = step_table(timer, steps_timed, B, args.regions, bf16, args.model)
-        # `roofline` = the hand-written OP that takes the largest share of the step -- its launches summed over every shape
-        # it runs at (linear_act_fwd runs once with and once without the in-register dropout mask: two entries of
-        # roofline_all, one op) -- not a favourite; library GEMMs (hipBLASLt through torch) are listed in roofline_all with
-        # their time and rate as well
-        ours = [e for e in entries if e["bound"] is not None and e["kernel"] != "library_gemm"]
-        by_op = {}
-        for e in ours:
-            by_op.setdefault(e["kernel"], []).append(e)
-        dominant = None
-        if by_op:
-            name, group = max(by_op.items(), key=lambda kv: sum(e["ms_per_step"] for e in kv[1]))
-            launches = sum(e["launches"] for e in group)
-            total_ms = sum(e["mean_ms"] * e["launches"] for e in group)
-            work = sum(e["achieved"] * e["mean_ms"] * e["launches"] for e in group)        # (rate x time = work, per entry)
-            lead = max(group, key=lambda e: e["ms_per_step"])
-            dominant = {"bound": lead["bound"], "achieved": round(work / total_ms, 2), "peak": lead["peak"], "unit": lead["unit"],
-                        "frac": round(work / total_ms / lead["peak"], 4),
-                        "traffic": lead["traffic"], "kernel": name, "mean_ms": round(total_ms / launches, 5),
-                        "launches": launches, "ms_per_step": round(sum(e["ms_per_step"] for e in group), 5),
-                        "shapes": [e["shape"] for e in group],
-                        "device_kernels": lead.get("device_kernels", PMC_KERNELS.get(name, []))}
-            for k in ("mfma_busy_pct", "valu_issue_pct_min", "traffic_stale"):
-                if k in lead:
-                    dominant[k] = lead[k]
-            if all("trace_ms" in e for e in group):      # the same op in the committed trace of the replayed step, launch-weighted
-                dominant["trace_ms"] = round(sum(e["trace_ms"] * e["launches"] for e in group) / launches, 5)
-        else:
-            dominant = dict(entries[0])
-        kernel_ms = sum(e["ms_per_step"] for e in entries)
-        lib_ms = sum(e["ms_per_step"] for e in entries if e["kernel"] == "library_gemm")
         ms_step = 1e3 * elapsed / args.steps
+        if rotate:
+            inputs = "%d rotating batches (%s)" % (ROTATE, "+1 device copy/step" if args.copy_inputs else
+                                                   "a step graph per batch slot, no copy")
+            inputs_note = ("`value` visits %d different resident batches in turn (%.0f MB of regions each: together beyond the "
+                           "256 MB Infinity Cache); %s" % (ROTATE, v.numel() * v.element_size() / 1e6,
+                                                           "one device-to-device copy into the replayed graphs' input buffers "
+                                                           "per step inside the timed region" if args.copy_inputs else
+                                                           "the forward + backward graph is captured once per batch slot and "
+                                                           "reads its slot in place (trainer input_slots), no copy"))
+            if resident is not None:         # (--full)
+                inputs += "; 1 resident batch: %.1f (%+.1f%%)" % (
+                    resident["value"], 100.0 * (resident["value"] / (world * B * args.steps / elapsed) - 1.0))
+                inputs_note += "; `resident_inputs` re-reads ONE batch (cache-resident)"
+        else:
+            inputs, inputs_note = "1 resident batch", "ONE resident batch re-read every step"
         result = {
             "metric": "VQA samples/sec (fwd+bwd), %s batch %d, %dx2048 regions%s"
                       % ("CoR2" if args.model == "cor2" else "ODA", B, args.regions,
@@ -1011,33 +1055,16 @@ def main():
                        "f32_products": ("fp32 MFMA (v_mfma_f32_16x16x4_f32)" if args.f32_products == "mfma" else
                                         "3xbf16 split, 6 partial products, fp32 accumulate"),
                        "library_gemms": __import__("vqa_playground_pytorch_amd.tuned_gemms", fromlist=["describe"]).describe(),
-                       "inputs": ("%d rotating batches (%s); 1 resident batch: %.1f (%+.1f%%)"
-                                  % (ROTATE, "+1 device copy/step" if args.copy_inputs else "a step graph per batch slot, no copy",
-                                     resident["value"], 100.0 * (resident["value"] / (world * B * args.steps / elapsed) - 1.0))
-                                  if resident is not None else "1 resident batch"),
-                       "inputs_note": ("`value` visits %d different resident batches in turn (%.0f MB of regions each: together "
-                                       "beyond the 256 MB Infinity Cache); %s; `resident_inputs` re-reads ONE batch "
-                                       "(cache-resident)" % (ROTATE, v.numel() * v.element_size() / 1e6,
-                                                             "one device-to-device copy into the replayed graphs' input buffers "
-                                                             "per step inside the timed region" if args.copy_inputs else
-                                                             "the forward + backward graph is captured once per batch slot and "
-                                                             "reads its slot in place (trainer input_slots), no copy"))
-                       if resident is not None else "ONE resident batch re-read every step"},
+                       "inputs": inputs, "inputs_note": inputs_note},
             "final_loss": round(final_loss, 3), "final_grad_norm": round(final_gnorm, 3),
-            "roofline": dominant,
-            "traffic_source": "profiles/%s_pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command "
-                              "(committed evidence; no profiler is attached in this run)" % EVIDENCE_TAG,
-            # how much of the step the per-kernel table accounts for (its durations come from the kernel-by-kernel pass,
-            # ms_per_step from the replayed graphs; the rest is framework glue: small element-wise kernels, copies, gaps)
-            "step_coverage": {"timed_ops_ms": round(kernel_ms, 3), "of_ms_per_step": round(kernel_ms / ms_step, 3),
-                              "library_gemm_ms": round(lib_ms, 3), "hand_written_ms": round(kernel_ms - lib_ms, 3)},
-            "roofline_all": entries,
         }
+        if args.full:
+            result.update(roofline_record(timer, args, B, bf16, graphed, ms_step))
         if resident is not None:
             result["resident_inputs"] = resident
         if world > 1:
             result["distributed"] = dist_info
-        if headline and B == BATCH and not args.no_sub_records and graphed:
+        if args.full and headline and B == BATCH and not args.no_sub_records and graphed:
             # the other single-GPU BASELINE configs, measured on this GPU in the same invocation (child runs of this file)
             result["sub_records"] = run_sub_records(args.steps, args.warmup, args.detail_file)
         if want_cpu:       # after the GPU sub-records: a 16-thread CPU job beside them cost the ODA record 12 % (host-bound replays)

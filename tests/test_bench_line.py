@@ -1,9 +1,11 @@
-"""bench.py's stdout contract: ONE compact JSON line under 2000 bytes that still carries `roofline` and `cpu_baseline`
-(the round-3 line grew to 21 KB and the driver recorded `parsed: null`), and the (kernel, grid) look-up of the committed
-counter tables."""
+"""bench.py's stdout contract: ONE compact JSON line under 2000 bytes that, with --full, still carries `roofline` and
+`cpu_baseline` (the round-3 line grew to 21 KB and the driver recorded `parsed: null`), and the (kernel, grid) look-up of
+the committed counter tables."""
 import json
 import os
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -247,3 +249,47 @@ def test_bench_refuses_an_empty_timed_region():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
                        timeout=300)
     assert r.returncode != 0 and "--steps must be at least 1" in r.stderr and "{" not in r.stdout
+
+
+def test_compact_line_of_a_plain_run_holds_no_full_only_parts(tmp_path, capsys):
+    """A run without --full measures nothing beyond its timed steps: its line carries the contract fields and the
+    configuration, and no empty `roofline` object stands in for the per-kernel pass it did not run."""
+    full = _canned(1)
+    for key in ("roofline", "traffic_source", "step_coverage", "roofline_all", "resident_inputs", "sub_records", "cpu_baseline"):
+        del full[key]
+    bench.emit(full, str(tmp_path / "bench_detail.json"))
+    out, _ = capsys.readouterr()
+    line = json.loads(out.strip().splitlines()[-1])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+        assert line[key] == full[key], key
+    assert full["config"]["workload"].startswith(line["config"]["workload"]) and "relation_mode" in line["config"]
+    assert not {"roofline", "cpu_baseline", "resident_inputs", "sub_records", "distributed"} & set(line)
+
+
+@pytest.mark.gpu
+def test_plain_run_leaves_the_extra_measurements_to_full(tmp_path):
+    """`bench.py` without --full times its steps and prints the line, nothing more: no roofline, resident-batch pass, CPU
+    baseline or sub-records.  With --full the same command adds the roofline of the per-kernel pass and the resident-batch
+    figure (sub-records run only at the headline batch, so a small batch leaves them out in both)."""
+    import subprocess
+    lines = {}
+    for mode in ("plain", "full"):
+        detail = tmp_path / ("%s.json" % mode)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "64",
+               "--no-cpu-baseline", "--detail-file", str(detail)] + (["--full"] if mode == "full" else [])
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert r.returncode == 0 and len(out) == 1, (mode, r.returncode, r.stdout[-1500:], r.stderr[-3000:])
+        lines[mode] = (json.loads(out[0]), json.load(open(detail)))
+    for mode, (line, full) in lines.items():
+        assert line["metric"].startswith("VQA samples/sec (fwd+bwd), CoR2 batch 64") and line["unit"] == "samples/s"
+        assert line["steps"] == 3 and line["warmup"] == 2 and line["dtype"] == "f32" and line["higher_is_better"] is True
+        assert abs(line["value"] - 64 * 1e3 / line["ms_per_step"]) <= 1e-2 * line["value"], mode
+        assert line["config"]["inputs"].startswith("4 rotating batches (a step graph per batch slot, no copy)"), mode
+        assert 0.0 < full["final_loss"] and "sub_records" not in line and "cpu_baseline" not in line
+    plain, plain_full = lines["plain"]
+    assert not {"roofline", "resident_inputs"} & set(plain)
+    assert not {"roofline", "roofline_all", "step_coverage", "resident_inputs"} & set(plain_full)
+    line, full = lines["full"]
+    assert 0 < line["roofline"]["frac"] < 1 and len(full["roofline_all"]) > 10 and line["resident_inputs"]["value"] > 0
+    assert "1 resident batch: " in line["config"]["inputs"]

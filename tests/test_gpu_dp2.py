@@ -65,11 +65,12 @@ def test_bench_two_rank_rehearsal_prints_a_valid_record(tmp_path):
     share cuda:0, gloo carries the collectives.  The first 8-GPU run must produce a valid record without a second try
     (VERDICT r04 item 6): the compact line parses, stays under 2 KB WITH the `distributed` block, says n_gpus = 2 and a global
     batch of 2 per-rank batches, and the block holds BOTH reduction schedules (single all-reduce / two-half backward with
-    the first all-reduce under the second half), `value` being the faster one."""
+    the first all-reduce under the second half), `value` being the faster one.  With --full, as here, the line also carries
+    the roofline of the per-kernel pass and the block the all-reduce timed on its own."""
     detail = tmp_path / "bench_detail.json"
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", VQA_ONE_GPU_REHEARSAL="1", VQA_DIST_BACKEND="gloo")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "3", "--batch", "64",
-           "--detail-file", str(detail)]
+           "--full", "--detail-file", str(detail)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
@@ -80,7 +81,7 @@ def test_bench_two_rank_rehearsal_prints_a_valid_record(tmp_path):
     assert line["dtype"] == "f32" and line["config"]["f32_products"].startswith("3xbf16 split")
     d = line["distributed"]
     assert d["nranks"] == 2 and d["backend"] == "gloo" and d["allreduce_payload_bytes"] >= 4 * 11940244
-    assert set(d["schedules"]) == {"single", "overlap"}
+    assert set(d["schedules"]) == {"single", "overlap"} and d["allreduce_ms_alone"] > 0
     rates = [s["value"] for s in d["schedules"].values()]
     assert all(v > 0 for v in rates) and abs(line["value"] - max(rates)) <= 1e-6 * max(rates)
     assert "roofline" in line and line["roofline"]["frac"] is not None and 0 < line["roofline"]["frac"] < 1

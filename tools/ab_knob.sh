@@ -5,7 +5,7 @@ K=${1:?knob}; VALS=${2:?values}; R=${3:-3}; S=${4:-100}; shift 4 2>/dev/null || 
 for i in $(seq 1 $R); do
   for v in $VALS; do
     export $K=$v
-    python3 bench.py --steps $S --warmup 10 --no-cpu-baseline --no-sub-records --detail-file /tmp/ab_detail.json "$@" 2>/dev/null > /tmp/ab_line.json
+    python3 bench.py --full --steps $S --warmup 10 --no-cpu-baseline --no-sub-records --detail-file /tmp/ab_detail.json "$@" 2>/dev/null > /tmp/ab_line.json
     python3 - "$K=$v" <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab_line.json"))

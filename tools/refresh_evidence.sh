@@ -79,11 +79,11 @@ for kind in ("traffic", "mfma"):
     print(kind, "fp32 MFMA engine rows merged:", sorted(rows))
 PY
 cd "$ROOT"
-timeout 900 python3 bench.py --detail-file "$OUT/bench_b512_mfma_detail.json" --f32-products mfma --steps 20 --warmup 5 --no-cpu-baseline --no-sub-records > "$OUT/bench_b512_mfma.json" 2> "$OUT/bench_b512_mfma.log"
-timeout 900 python3 bench.py --detail-file "$OUT/bench_oda_b512_mfma_detail.json" --model oda --f32-products mfma --steps 20 --warmup 5 --no-cpu-baseline --no-sub-records > "$OUT/bench_oda_b512_mfma.json" 2> "$OUT/bench_oda_b512_mfma.log"
+timeout 900 python3 bench.py --full --detail-file "$OUT/bench_b512_mfma_detail.json" --f32-products mfma --steps 20 --warmup 5 --no-cpu-baseline --no-sub-records > "$OUT/bench_b512_mfma.json" 2> "$OUT/bench_b512_mfma.log"
+timeout 900 python3 bench.py --full --detail-file "$OUT/bench_oda_b512_mfma_detail.json" --model oda --f32-products mfma --steps 20 --warmup 5 --no-cpu-baseline --no-sub-records > "$OUT/bench_oda_b512_mfma.json" 2> "$OUT/bench_oda_b512_mfma.log"
 cd /tmp
 rm -rf /tmp/kt_mfmaeng
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_mfmaeng -- python3 "$ROOT/bench.py" --f32-products mfma --steps 20 --warmup 5 --no-cpu-baseline --no-sub-records --detail-file /tmp/kt_detail.json > "$OUT/kt_mfmaeng.log" 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_mfmaeng -- python3 "$ROOT/bench.py" --full --f32-products mfma --steps 20 --warmup 5 --no-cpu-baseline --no-sub-records --detail-file /tmp/kt_detail.json > "$OUT/kt_mfmaeng.log" 2>&1
 f=$(find /tmp/kt_mfmaeng -name "*kernel_stats.csv" | sort | sed -n 1p)
 [ -n "$f" ] && cp "$f" "$OUT/bench_b512_mfma_kernel_stats.csv"
 python3 "$ROOT/tools/by_grid.py" /tmp/kt_mfmaeng 1 "hand-written kernels, per-dispatch durations by (kernel, grid work-items); rocprofv3 --kernel-trace of bench.py --f32-products mfma --steps 20 --warmup 5 --no-cpu-baseline (the last column is the total over the run)" > "$OUT/vqa_kernels_by_grid_mfma.txt" 2>&1
@@ -94,8 +94,9 @@ fi
 if want bench; then
 # 2. bench lines
 cd "$ROOT"
-# (bench.py prints its compact line on stdout and the full record on stderr + --detail-file)
-run() { name=$1; shift; timeout 900 python3 bench.py --detail-file "$OUT/${name}_detail.json" "$@" > "$OUT/$name.json" 2> "$OUT/$name.log"; }
+# (bench.py prints its compact line on stdout and the full record on stderr + --detail-file; --full: with the roofline,
+#  resident-batch, sub-record and CPU-baseline measurements the published records carry)
+run() { name=$1; shift; timeout 900 python3 bench.py --full --detail-file "$OUT/${name}_detail.json" "$@" > "$OUT/$name.json" 2> "$OUT/$name.log"; }
 run bench_default
 run bench_b512 --steps 20 --warmup 5
 VQA_HEAD=legacy run bench_b512_legacy_head --steps 20 --warmup 5 --no-cpu-baseline --no-sub-records
@@ -126,7 +127,7 @@ cd /tmp
 for mode in graph eager; do
   extra=""; [ $mode = eager ] && extra="--no-graph"
   rm -rf /tmp/kt_$mode
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$mode -- python3 "$ROOT/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-sub-records --detail-file /tmp/kt_detail.json $extra > "$OUT/kt_$mode.log" 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$mode -- python3 "$ROOT/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-sub-records --detail-file /tmp/kt_detail.json $extra > "$OUT/kt_$mode.log" 2>&1
   f=$(find /tmp/kt_$mode -name "*kernel_stats.csv" | sort | sed -n 1p)
   [ -n "$f" ] && cp "$f" "$OUT/bench_b512_${mode}_kernel_stats.csv"
   python3 "$ROOT/tools/by_grid.py" /tmp/kt_$mode 1 "hand-written kernels, per-dispatch durations by (kernel, grid work-items); rocprofv3 --kernel-trace of bench.py --steps 20 --warmup 5 --no-cpu-baseline $extra (the last column is the total over the run)" "$OUT/trace_$mode.json" > "$OUT/vqa_kernels_by_grid_$mode.txt" 2>&1
@@ -137,7 +138,7 @@ done
 for cfg in "oda_b512|--model oda" "bf16_n100_b128|--dtype bf16 --regions 100 --batch 128"; do
   name=${cfg%%|*}; args=${cfg#*|}
   rm -rf /tmp/kt_$name
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$name -- python3 "$ROOT/bench.py" $args --steps 20 --warmup 5 --no-cpu-baseline --no-sub-records --detail-file /tmp/kt_detail.json > "$OUT/kt_$name.log" 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$name -- python3 "$ROOT/bench.py" --full $args --steps 20 --warmup 5 --no-cpu-baseline --no-sub-records --detail-file /tmp/kt_detail.json > "$OUT/kt_$name.log" 2>&1
   f=$(find /tmp/kt_$name -name "*kernel_stats.csv" | sort | sed -n 1p)
   [ -n "$f" ] && cp "$f" "$OUT/bench_${name}_kernel_stats.csv"
   python3 "$ROOT/tools/by_grid.py" /tmp/kt_$name 1 "hand-written kernels, per-dispatch durations by (kernel, grid work-items); rocprofv3 --kernel-trace of bench.py $args --steps 20 --warmup 5 --no-cpu-baseline (the last column is the total over the run)" "$OUT/trace_$name.json" > "$OUT/vqa_kernels_by_grid_$name.txt" 2>&1
