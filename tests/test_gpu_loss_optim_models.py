@@ -1,0 +1,186 @@
+"""The driver's other criteria and optimizers through the whole GPU train step: CoR2 and ODA trained for three steps with
+(BCE, sgd), (CE, rms) and (KLD, sgd) against the reference-faithful oracle models on the CPU under torch's own criterion and
+optimizer (train.py:63-86 order), hipGraph replay against kernel-by-kernel steps, and the checkpoint round trip."""
+import os
+import warnings
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import reference_faithful as RF
+from oracle import seeded
+
+pytestmark = pytest.mark.gpu
+
+RTOL = 1e-3          # losses and gradient norms: the bar of tests/test_gpu_models.py
+GAMMA = 0.5 ** (1 / 50000)
+
+# RMSprop, like Adam, divides a gradient by its own magnitude: a mathematically zero gradient (a bias in front of the softmax
+# over regions is a constant shift) is ~1e-9 rounding noise on both sides and becomes +-lr steps of unrelated signs.  Exactly
+# these tensors are left out of the weight comparison under RMSprop, by name; under SGD nothing is.
+ZERO_GRADIENT = {
+    "cor2": {"fusion_vq%d.list_linear1.%d.linear.bias" % (s, r) for s in (1, 2) for r in (0, 1)}
+            | {"att%d.conv_att.conv.bias" % s for s in (1, 2)},
+    "oda": {"att.conv_att.conv.bias"},
+}
+
+
+def dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda:0")
+
+
+def build(cls, nans):
+    from vqa_playground_pytorch_amd import CoR2Model, ODAModel
+    model = {"cor2": CoR2Model, "oda": ODAModel}[cls](["PAD", "UNK"], nans)
+    return seeded.load_state(model, 0).eval().to(dev())
+
+
+def batch(B, C, seed, loss):
+    v, q, a = (torch.from_numpy(x) for x in seeded.seeded_inputs(B, answers=C, seed=seed))
+    if loss == "CE":
+        a = torch.from_numpy(np.random.RandomState(seed).randint(0, C, B).astype(np.int64))
+    return v, q, a
+
+
+def criterion(loss, logits, a):
+    if loss == "BCE":
+        return torch.nn.BCELoss()(torch.sigmoid(logits), a)
+    if loss == "CE":
+        return torch.nn.CrossEntropyLoss()(logits, a)
+    return F.kl_div(F.log_softmax(logits, dim=1), a, reduction="sum")
+
+
+def oracle_steps(cls, loss, optim, batches, lr):
+    model = seeded.load_state({"cor2": RF.CoR2Oracle, "oda": RF.ODAOracle}[cls](300), 0).eval()
+    params = [p for p in model.parameters() if p.requires_grad]
+    opt = torch.optim.SGD(params, lr=lr, momentum=0.9) if optim == "sgd" else torch.optim.RMSprop(params, lr=lr)
+    sch = torch.optim.lr_scheduler.ExponentialLR(opt, GAMMA)
+    losses, norms = [], []
+    for v, q, a in batches:
+        value = criterion(loss, model({"v": v, "q": q}), a)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            sch.step()
+        opt.zero_grad()
+        value.backward()
+        norms.append(float(torch.nn.utils.clip_grad_norm_(model.parameters(), 0.25)))
+        opt.step()
+        losses.append(value.item())
+    return losses, norms, opt.param_groups[0]["lr"], {n: p.detach().double().norm().item() for n, p in model.named_parameters()}
+
+
+@pytest.mark.parametrize("loss,optim", [("BCE", "sgd"), ("CE", "rms"), ("KLD", "sgd")])
+@pytest.mark.parametrize("cls", ["cor2", "oda"])
+def test_three_steps_match_the_oracle_under_torchs_classes(cls, loss, optim, measured):
+    from vqa_playground_pytorch_amd.trainer import DataParallelTrainer
+    batches = [batch(4, 300, 101 + step, loss) for step in range(3)]
+    want_losses, want_norms, want_lr, want_w = oracle_steps(cls, loss, optim, batches, 1e-4)
+    model = build(cls, 300)
+    tr = DataParallelTrainer(model, lr=1e-4, clip=0.25, loss=loss, optim=optim)
+    losses, norms = [], []
+    for v, q, a in batches:
+        value, norm = tr.step({"v": v.to(dev()), "q_idxes": q.to(dev())}, a.to(dev()))
+        losses.append(value.item())
+        norms.append(norm.item())
+    e_loss = max(abs(x - y) / abs(y) for x, y in zip(losses, want_losses))
+    e_norm = max(abs(x - y) / abs(y) for x, y in zip(norms, want_norms))
+    skip = ZERO_GRADIENT[cls] if optim == "rms" else set()
+    names = dict(model.named_parameters())
+    assert skip <= set(names), skip - set(names)
+    e_w, worst = 0.0, None
+    for name, p in names.items():
+        if name in skip:
+            continue
+        e = abs(p.detach().double().norm().item() - want_w[name]) / want_w[name]
+        if e > e_w:
+            e_w, worst = e, name
+    measured("%s %s/%s loss rel" % (cls, loss, optim), e_loss, RTOL)
+    measured("%s %s/%s grad norm rel" % (cls, loss, optim), e_norm, RTOL)
+    measured("%s %s/%s weight norm rel" % (cls, loss, optim), e_w, 1e-5, worst or "")
+    assert e_loss <= RTOL and e_norm <= RTOL
+    assert abs(tr.lr - want_lr) <= 1e-12 * tr.lr
+    assert e_w <= 1e-5, worst
+
+
+@pytest.mark.parametrize("loss,optim", [("BCE", "rms"), ("CE", "sgd")])
+def test_graph_replay_equals_eager_steps_on_the_grid(loss, optim):
+    """B = 64, seven steps: the replayed step (lr read from the step block on the device) follows the kernel-by-kernel one.  Not
+    bitwise, for the reason tests/test_gpu_models.py::test_graph_replay_equals_eager_steps gives (float atomics in the d_alpha
+    reductions; RMSprop, like Adam, turns the last bits of near-zero gradients into +-lr steps), hence its bars and its small lr.
+    With topk=(1, 5), accuracy() agrees with torch.topk on last_logits."""
+    from vqa_playground_pytorch_amd.trainer import DataParallelTrainer
+    v, q, a = (t.to(dev()) for t in batch(64, 300, 21, loss))
+    out = {}
+    for mode in (False, True):
+        model = build("cor2", 300)
+        tr = DataParallelTrainer(model, lr=2e-5, clip=0.25, graph=mode, loss=loss, optim=optim, topk=(1, 5))
+        steps = []
+        for step in range(7):
+            value, norm = tr.step({"v": v, "q_idxes": q}, a)
+            steps.append((value.item(), norm.item()))
+            z = tr.last_logits.cpu()
+            t = a.cpu() if loss == "CE" else a.cpu().max(1).indices
+            pred = z.topk(5, 1, True, True).indices
+            want = [100.0 * (pred[:, :k] == t[:, None]).any(1).sum().item() / 64 for k in (1, 5)]
+            assert list(tr.accuracy()) == want
+        if mode:
+            assert tr._graph is not None, "step was not captured"
+            assert tr.graph_nodes and all("memset" not in c for c in tr.graph_nodes.values())
+        out[mode] = (steps, [p.detach().clone() for p in model.parameters()], tr.lr)
+    for (l0, n0), (l1, n1) in zip(out[False][0], out[True][0]):
+        assert abs(l0 - l1) <= 1e-4 * abs(l0) and abs(n0 - n1) <= 1e-4 * max(abs(n0), 1e-6)
+    assert out[False][2] == out[True][2]
+    for p0, p1 in zip(out[False][1], out[True][1]):
+        assert (p0 - p1).abs().max().item() <= 2e-3 * max(p0.abs().max().item(), 1e-3)
+
+
+@pytest.mark.parametrize("optim", ["sgd", "rms"])
+def test_checkpoint_round_trip(optim, tmp_path):
+    """Save after two steps, load into a fresh trainer over other initial weights: the optimizer file is what torch's own
+    optimizer writes and reads, and the third step is bitwise the writer's.  B = 64: the smallest batch at which the step is
+    bitwise reproducible at all (below VQA_K3_FUSED_MIN_B the attention-pool backward adds its partial sums with float atomics
+    in arrival order: tests/test_gpu_models.py::test_step_is_bitwise_reproducible_and_bf16_transport_is_the_fp32_step)."""
+    from vqa_playground_pytorch_amd import CoR2Model
+    from vqa_playground_pytorch_amd.trainer import DataParallelTrainer
+    model = build("cor2", 300)
+    tr = DataParallelTrainer(model, lr=1e-4, clip=0.25, loss="BCE", optim=optim)
+    data = [tuple(t.to(dev()) for t in batch(64, 300, 40 + i, "BCE")) for i in range(3)]
+    for v, q, a in data[:2]:
+        tr.step({"v": v, "q_idxes": q}, a)
+    path = tr.save_checkpoint({"epoch": 1, "exp_logger": None}, str(tmp_path))
+    sd = torch.load(os.path.join(path, "ckpt_optim.pth.tar"))
+
+    # torch's own optimizer of this version writes the same keys, and accepts the file
+    params = [p for p in model.parameters() if p.requires_grad]
+    clones = [torch.nn.Parameter(p.detach().cpu().clone()) for p in params]
+    stock = torch.optim.SGD(clones, lr=1e-4, momentum=0.9) if optim == "sgd" else torch.optim.RMSprop(clones, lr=1e-4)
+    torch.optim.lr_scheduler.ExponentialLR(stock, GAMMA)
+    assert set(sd["param_groups"][0]) == set(stock.state_dict()["param_groups"][0])
+    stock.load_state_dict(sd)
+    buf, key = (tr.flat.m, "momentum_buffer") if optim == "sgd" else (tr.flat.v, "square_avg")
+    assert (tr.flat.v if optim == "sgd" else tr.flat.m) is None          # the unused moment buffer is not allocated
+    where = {id(p): o for p, o in zip(tr.flat.params, tr.flat.offsets)}
+    for p, c in zip(params, clones):
+        st = stock.state[c]
+        assert torch.equal(st[key], buf[where[id(p)]:where[id(p)] + p.numel()].view_as(p).cpu())
+        if optim == "rms":
+            assert st["step"].dtype == torch.float32 and st["step"].dim() == 0 and float(st["step"]) == 2.0
+    other_kind = DataParallelTrainer(build("cor2", 300), lr=1e-4, optim="adam")
+    with pytest.raises(ValueError, match="belongs to optim"):
+        other_kind.load_optimizer_state_dict(sd)
+
+    torch.manual_seed(7)
+    other = CoR2Model(["PAD", "UNK"], 300).eval().to(dev())
+    tr2 = DataParallelTrainer(other, lr=1e-4, clip=0.25, loss="BCE", optim=optim)
+    assert tr2.load_checkpoint(path) is None
+    assert torch.equal(tr2.flat.p, tr.flat.p) and torch.equal(buf, tr2.flat.m if optim == "sgd" else tr2.flat.v)
+    tr.iteration = 0                       # the reference's schedule restarts on resume
+    v, q, a = data[2]
+    l1, n1 = tr.step({"v": v, "q_idxes": q}, a)
+    l2, n2 = tr2.step({"v": v, "q_idxes": q}, a)
+    assert tr.lr == tr2.lr
+    assert torch.equal(l1, l2) and torch.equal(n1, n2)
+    assert torch.equal(tr.flat.p.view(torch.int32), tr2.flat.p.view(torch.int32))

@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark of libvqa_mi355x.so at the BASELINE shapes (B=512, N=36, D=2048, L=310, H=510, G=4, R=2).
 Interleaved rounds in ONE process (guide rule 24); prints median / min per variant and the roofline fraction.
 
-    python tools/kbench.py [--only k4fwd,k4bwd,k1,k2,k3,k3a,k5 | bf16 | head] [--tiles 128x128,64x64] [--rounds 20]
+    python tools/kbench.py [--only k4fwd,k4bwd,k1,k2,k3,k3a,k5,optim,loss | bf16 | head] [--tiles 128x128,64x64] [--rounds 20]
 """
 import argparse
 import os
@@ -263,6 +263,30 @@ def main():
             vq = ((vl[:, :, None, :] - vl[:, None, :, :]) * ql[:, None, None, :]).reshape(B, N, N * L)
             return torch.nn.functional.linear(torch.nn.functional.dropout(vq, 0.5, True), wk, bk)
         report("reference: torch broadcast difference + dropout + linear (materialises [B,36,11160])", timeit({"torch fwd p=0.5": torch_ref}, args.rounds), 2 * G * N * N * L * B, "TF")
+    if want("optim"):
+        # the optimizer pass over CoR2's flat parameter buffer: Adam moves 28 B per parameter, SGD and RMSprop 20
+        n = 11940244
+        p, gflat = torch.randn(n, device=dev), torch.randn(n, device=dev)
+        m, vv = torch.zeros(n, device=dev), torch.rand(n, device=dev)
+        nc = torch.tensor([1.0, 0.5], device=dev)
+        res = timeit({"adam": lambda: ops.adam_step(p, gflat, m, vv, nc, 1e-4, 0.9, 0.999, 1e-8, 3),
+                      "sgd": lambda: ops.sgd_step(p, gflat, m, nc, 1e-4, 0.9),
+                      "rmsprop": lambda: ops.rmsprop_step(p, gflat, vv, nc, 1e-4, 0.99, 1e-8)}, args.rounds)
+        report("optimizer pass, %d parameters: Adam (28 B each)" % n, {"adam": res["adam"]}, 28 * n, "GB")
+        report("optimizer pass, %d parameters: SGD / RMSprop (20 B each)" % n, {k: res[k] for k in ("sgd", "rmsprop")}, 20 * n, "GB")
+    if want("loss"):
+        # the loss row kernels at the two answer vocabularies: KLD and BCE read z and a and write dz, CE reads z and writes dz
+        for C in (2000, 3000):
+            z = torch.randn(B, C, device=dev) * 4
+            a = torch.softmax(torch.randn(B, C, device=dev) * 2, 1)
+            lab = torch.randint(0, C, (B,), device=dev)
+            res = timeit({"kld": lambda: ops.kld_sum_loss_and_grad(z, a), "kld + hits": lambda: ops.kld_sum_loss_and_grad_hits(z, a, 5),
+                          "bce": lambda: ops.bce_mean_loss_and_grad(z, a), "bce + hits": lambda: ops.bce_mean_loss_and_grad_hits(z, a, 5),
+                          "ce": lambda: ops.ce_mean_loss_and_grad(z, lab, check=False),
+                          "ce + hits": lambda: ops.ce_mean_loss_and_grad_hits(z, lab, 5, check=False)}, args.rounds)
+            report("loss + gradient [%d,%d] (rows + total; includes the wrapper's allocations): 3 arrays" % (B, C),
+                   {k: res[k] for k in ("kld", "kld + hits", "bce", "bce + hits")}, 3 * B * C * 4, "GB")
+            report("loss + gradient [%d,%d]: 2 arrays" % (B, C), {k: res[k] for k in ("ce", "ce + hits")}, 2 * B * C * 4, "GB")
     if want("copy"):
         y = torch.empty_like(v)
         fns = {"torch copy 151MB": lambda: y.copy_(v)}

@@ -156,10 +156,20 @@ SIGNATURES = {
     "vqa_predict_topk_workspace_bytes": (_c_sz, [_c_i, _c_i]),
     "vqa_predict_topk": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_f, _c_sz, _c_i, _c_i, _c_st]),
     "vqa_predict_candidates": (_c_i, [_c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_st]),
+    "vqa_mean_loss_workspace_bytes": (_c_sz, [_c_i]),
+    "vqa_mean_loss_hits_workspace_bytes": (_c_sz, [_c_i, _c_i]),
+    "vqa_bce_mean_loss": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_fl, _c_f, _c_sz, _c_i, _c_i, _c_st]),
+    "vqa_bce_mean_loss_hits": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_fl, _c_f, _c_sz, _c_i, _c_i, _c_st]),
+    "vqa_ce_mean_loss": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_fl, _c_f, _c_sz, _c_i, _c_i, _c_st]),
+    "vqa_ce_mean_loss_hits": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_fl, _c_f, _c_sz, _c_i, _c_i, _c_st]),
     "vqa_grad_norm_workspace_bytes": (_c_sz, []),
     "vqa_grad_norm_clip_coef": (_c_i, [_c_f, _c_sz, _c_fl, _c_f, _c_f, _c_sz, _c_st]),
     "vqa_adam_step": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_sz, _c_f, _c_fl, _c_fl, _c_fl, _c_fl, _c_i, _c_st]),
     "vqa_adam_step_dyn": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_sz, _c_f, _c_f, _c_fl, _c_fl, _c_fl, _c_st]),
+    "vqa_sgd_step": (_c_i, [_c_f, _c_f, _c_f, _c_sz, _c_f, _c_fl, _c_fl, _c_st]),
+    "vqa_sgd_step_dyn": (_c_i, [_c_f, _c_f, _c_f, _c_sz, _c_f, _c_f, _c_fl, _c_st]),
+    "vqa_rmsprop_step": (_c_i, [_c_f, _c_f, _c_f, _c_sz, _c_f, _c_fl, ctypes.c_double, _c_fl, _c_st]),
+    "vqa_rmsprop_step_dyn": (_c_i, [_c_f, _c_f, _c_f, _c_sz, _c_f, _c_f, ctypes.c_double, _c_fl, _c_st]),
 }
 
 _lock = threading.Lock()

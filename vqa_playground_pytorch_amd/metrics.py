@@ -18,8 +18,14 @@ def _order(logits):
 
 
 def target_rank(logits, target):
-    """int64 [B]: the rank of each row's target class among its logits (torch ops; any device)."""
-    t = torch.max(target, 1).indices
+    """int64 [B]: the rank of each row's target class among its logits (torch ops; any device).  A 1-D integer target holds
+    the classes themselves (sampled answers, train.py:30-32 leaves them as they are)."""
+    if target.dim() == 1:
+        if target.is_floating_point() or target.size(0) != logits.size(0):
+            raise ValueError("a 1-D target must hold one integer class per row, got %s %s" % (target.dtype, tuple(target.shape)))
+        t = target.to(torch.int64)
+    else:
+        t = torch.max(target, 1).indices
     zt = logits.gather(1, t[:, None])
     col = torch.arange(logits.size(1), device=logits.device)
     lower = col[None, :] < t[:, None]
@@ -38,7 +44,7 @@ def _check_k(C, k):
 
 
 def topk_hits(logits, target, kmax):
-    """int32 [kmax]: hits[j] = rows whose target ranks <= j."""
+    """int32 [kmax]: hits[j] = rows whose target ranks <= j.  target: [B,C] soft targets, or (CPU tensors) integer classes [B]."""
     logits = logits.detach()
     _check_k(logits.size(1), int(kmax))
     if logits.is_cuda:

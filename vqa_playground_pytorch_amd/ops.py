@@ -1817,6 +1817,85 @@ def kld_sum_loss_and_grad_hits(logits, target, kmax):
     return loss, d_logits, hits
 
 
+def _mean_loss(kind, logits, target, scale, kmax):
+    """The shared body of the BCE / CE wrappers below: checks, buffers, one launch -> (loss, d_logits, hits or None)."""
+    name = kind + "_mean_loss"
+    for what, t, dtype in (("logits", logits, torch.float32), ("target", target, torch.float32) if kind == "bce" else
+                           ("labels", target, torch.int64)):
+        if isinstance(t, torch.Tensor) and t.dtype != dtype:
+            raise ValueError("%s: %s must be %s, got %s" % (name, what, dtype, t.dtype))
+    lg = _prep("logits", logits.detach())
+    if kind == "bce":
+        target = _prep("target", target)
+        if lg.dim() != 2 or target.shape != lg.shape:
+            raise ValueError("%s: logits and target must both be [B,C], got %s and %s" % (name, tuple(lg.shape), tuple(target.shape)))
+    else:
+        target = _prep("labels", target, (torch.int64,))
+        if lg.dim() != 2 or target.dim() != 1 or target.size(0) != lg.size(0):
+            raise ValueError("%s: logits [B,C] and int64 labels [B] expected, got %s and %s"
+                             % (name, tuple(lg.shape), tuple(target.shape)))
+    B, C = lg.shape
+    if B == 0 or C == 0:
+        raise ValueError("%s: empty logits %s" % (name, tuple(lg.shape)))
+    scale = float(scale)
+    if not 0.0 < scale < float("inf"):
+        raise ValueError("%s: scale=%r must be positive and finite" % (name, scale))
+    lib = _lib.lib()
+    loss = torch.empty((), device=lg.device, dtype=torch.float32)
+    d_logits = torch.empty_like(lg)
+    if kmax is None:
+        nbytes = lib.vqa_mean_loss_workspace_bytes(B)
+        ws = torch.empty(nbytes // 4, device=lg.device, dtype=torch.float32)
+        _launch(name, (B, C, True), getattr(lib, "vqa_" + name), _p(lg), _p(target), _p(loss), _p(d_logits), scale, _p(ws), nbytes,
+                B, C)
+        return loss, d_logits, None
+    kmax = int(kmax)
+    _check_k(name + "_hits", C, kmax)
+    hits = torch.empty(kmax, device=lg.device, dtype=torch.int32)
+    nbytes = lib.vqa_mean_loss_hits_workspace_bytes(B, kmax)
+    ws = torch.empty(nbytes // 4, device=lg.device, dtype=torch.float32)
+    _launch(name + "_hits", (B, C, kmax), getattr(lib, "vqa_" + name + "_hits"), _p(lg), _p(target), _p(loss), _p(d_logits),
+            _p(hits), kmax, scale, _p(ws), nbytes, B, C)
+    return loss, d_logits, hits
+
+
+def check_labels(labels, C):
+    """CrossEntropyLoss's caller error, raised on the host: a label outside [0, C).  Reads the labels back (a device
+    synchronisation), so the train step calls it outside its captured part only."""
+    if labels.numel() and not bool(((labels >= 0) & (labels < C)).all()):
+        raise ValueError("ce_mean_loss: labels must lie in [0, C=%d), got min %d max %d" % (C, int(labels.min()), int(labels.max())))
+
+
+def bce_mean_loss_and_grad(logits, target, scale=None):
+    """(loss, dL/dlogits) of nn.BCELoss()(sigmoid(logits), target) (train.py:522-534) from ONE pass, outside autograd, in
+    the stable softplus form.  ``scale`` defaults to 1 / (B * C), the mean over this batch; a data-parallel rank passes
+    1 / (B_global * C) so that the summed gradients are the global mean's."""
+    B, C = logits.shape[0], logits.shape[-1]
+    return _mean_loss("bce", logits, target, 1.0 / max(B * C, 1) if scale is None else scale, None)[:2]
+
+
+def bce_mean_loss_and_grad_hits(logits, target, kmax, scale=None):
+    """bce_mean_loss_and_grad (bitwise the same loss and d_logits) plus hits int32[kmax] as kld_sum_loss_and_grad_hits counts them."""
+    B, C = logits.shape[0], logits.shape[-1]
+    return _mean_loss("bce", logits, target, 1.0 / max(B * C, 1) if scale is None else scale, kmax)
+
+
+def ce_mean_loss_and_grad(logits, labels, scale=None, check=True):
+    """(loss, dL/dlogits) of nn.CrossEntropyLoss()(logits, labels) (train.py:519-520) from ONE pass, outside autograd; labels
+    int64 [B].  ``scale`` defaults to 1 / B.  check=False skips the host-side range check of the labels (under graph capture,
+    where nothing may be read back; the kernel clamps the index)."""
+    if check and isinstance(labels, torch.Tensor) and labels.dtype == torch.int64 and logits.dim() == 2:
+        check_labels(labels, logits.size(1))
+    return _mean_loss("ce", logits, labels, 1.0 / max(logits.shape[0], 1) if scale is None else scale, None)[:2]
+
+
+def ce_mean_loss_and_grad_hits(logits, labels, kmax, scale=None, check=True):
+    """ce_mean_loss_and_grad (bitwise the same loss and d_logits) plus hits int32[kmax]: hits[j] = rows whose label ranks <= j."""
+    if check and isinstance(labels, torch.Tensor) and labels.dtype == torch.int64 and logits.dim() == 2:
+        check_labels(labels, logits.size(1))
+    return _mean_loss("ce", logits, labels, 1.0 / max(logits.shape[0], 1) if scale is None else scale, kmax)
+
+
 def predict_topk(logits, k, target=None, probs=True):
     """The k best columns of every row in order (int64 [B,k]; column 0 = argmax), the softmax over the whole row at those
     columns ([B,k], or None with probs=False) and, with a target [B,C], its top-j hits (int32 [k]; else None)."""
@@ -1876,6 +1955,46 @@ def adam_step_dyn(p_flat, g_flat, m_flat, v_flat, norm_and_coef, step_scalars, b
     """adam_step with {lr/(1-b1^t), 1/sqrt(1-b2^t)} read from the device tensor ``step_scalars`` (graph replays)."""
     _launch("adam_step_dyn", (p_flat.numel(),), _lib.lib().vqa_adam_step_dyn, _p(p_flat), _p(g_flat), _p(m_flat),
             _p(v_flat), p_flat.numel(), _p(norm_and_coef), _p(step_scalars), float(beta1), float(beta2), float(eps))
+
+
+def _flat_triple(name, p_flat, g_flat, s_flat):
+    for what, t in (("p", p_flat), ("g", g_flat), ("state", s_flat)):
+        if isinstance(t, torch.Tensor) and t.dtype != torch.float32:
+            raise ValueError("%s: %s must be torch.float32, got %s" % (name, what, t.dtype))
+        if _prep(what, t) is not t:
+            raise ValueError("%s: %s must be contiguous" % (name, what))
+        if t.numel() != p_flat.numel() or t.numel() == 0:
+            raise ValueError("%s: p, g and the state buffer must hold the same, non-zero number of elements" % name)
+
+
+def sgd_step(p_flat, g_flat, buf_flat, norm_and_coef, lr, momentum=0.9):
+    """One fused torch.optim.SGD(momentum) update of the flat parameter buffer on gradients scaled by norm_and_coef[1]
+    (None: unscaled): buf = momentum * buf + g, p -= lr * buf (train.py:288, :86)."""
+    _flat_triple("sgd_step", p_flat, g_flat, buf_flat)
+    _launch("sgd_step", (p_flat.numel(),), _lib.lib().vqa_sgd_step, _p(p_flat), _p(g_flat), _p(buf_flat), p_flat.numel(),
+            _p(norm_and_coef), float(lr), float(momentum))
+
+
+def sgd_step_dyn(p_flat, g_flat, buf_flat, norm_and_coef, step_scalars, momentum=0.9):
+    """sgd_step with lr read from word 0 of the device tensor ``step_scalars`` (graph replays)."""
+    _flat_triple("sgd_step_dyn", p_flat, g_flat, buf_flat)
+    _launch("sgd_step_dyn", (p_flat.numel(),), _lib.lib().vqa_sgd_step_dyn, _p(p_flat), _p(g_flat), _p(buf_flat), p_flat.numel(),
+            _p(norm_and_coef), _p(step_scalars), float(momentum))
+
+
+def rmsprop_step(p_flat, g_flat, sq_flat, norm_and_coef, lr, alpha=0.99, eps=1e-8):
+    """One fused torch.optim.RMSprop update (momentum 0, not centered) of the flat parameter buffer on gradients scaled by
+    norm_and_coef[1] (None: unscaled): sq = alpha * sq + (1 - alpha) * g^2, p -= lr * g / (sqrt(sq) + eps) (train.py:290, :86)."""
+    _flat_triple("rmsprop_step", p_flat, g_flat, sq_flat)
+    _launch("rmsprop_step", (p_flat.numel(),), _lib.lib().vqa_rmsprop_step, _p(p_flat), _p(g_flat), _p(sq_flat), p_flat.numel(),
+            _p(norm_and_coef), float(lr), float(alpha), float(eps))
+
+
+def rmsprop_step_dyn(p_flat, g_flat, sq_flat, norm_and_coef, step_scalars, alpha=0.99, eps=1e-8):
+    """rmsprop_step with lr read from word 0 of the device tensor ``step_scalars`` (graph replays)."""
+    _flat_triple("rmsprop_step_dyn", p_flat, g_flat, sq_flat)
+    _launch("rmsprop_step_dyn", (p_flat.numel(),), _lib.lib().vqa_rmsprop_step_dyn, _p(p_flat), _p(g_flat), _p(sq_flat),
+            p_flat.numel(), _p(norm_and_coef), _p(step_scalars), float(alpha), float(eps))
 
 
 host_seed_draws = 0  # bumped whenever a kernel's dropout seed is drawn on the host (such a step cannot be graph-replayed)

@@ -131,7 +131,7 @@ class FlatState:
     multi-tensor copy (cheaper than zero + ~70 accumulate-adds), which is then the all-reduce payload and the
     input of the fused clip + Adam kernels (csrc/optimizer.hip)."""
 
-    def __init__(self, params, stack_groups=()):
+    def __init__(self, params, stack_groups=(), moments=("m", "v")):
         # members of a stack group (same-shaped parameters that layers.my_linears stacks for one batched GEMM) are laid
         # out next to each other, in group order, so that the stack is a strided view of this buffer (ops.StackParams)
         params = [p for p in params if p.requires_grad]
@@ -165,8 +165,9 @@ class FlatState:
         self.offsets = offs
         self.p = torch.zeros(off, device=dev, dtype=torch.float32)
         self.g = torch.zeros(off, device=dev, dtype=torch.float32)
-        self.m = torch.zeros(off, device=dev, dtype=torch.float32)
-        self.v = torch.zeros(off, device=dev, dtype=torch.float32)
+        # the optimizer's state: Adam keeps both moments, SGD only m (its momentum buffer), RMSprop only v (its square average)
+        self.m = torch.zeros(off, device=dev, dtype=torch.float32) if "m" in moments else None
+        self.v = torch.zeros(off, device=dev, dtype=torch.float32) if "v" in moments else None
         self.g_views = []
         with torch.no_grad():
             for p, o in zip(self.params, offs):
@@ -237,8 +238,18 @@ class DataParallelTrainer:
     EAGER_STEPS_BEFORE_CAPTURE = 2
 
     def __init__(self, model, lr=1e-4, clip=0.25, gamma=0.5 ** (1 / 50000), broadcast=True, group=None,
-                 fused_adam=None, graph=False, adopt_inputs=False, overlap=None, input_slots=1, topk=None):
+                 fused_adam=None, graph=False, adopt_inputs=False, overlap=None, input_slots=1, topk=None,
+                 loss="KLD", optim="adam", lr_scheduler=True):
         self.model = model
+        # the reference driver's grid (train.py:286-299, :519-548): loss = KLD (sum over the batch) | BCE | CE (means over the
+        # GLOBAL batch), optim = adam | sgd (momentum 0.9) | rms, lr_scheduler = the per-iteration ExponentialLR on or off.
+        # The defaults are the step this trainer always ran: the same launches, the same graph nodes, the same bits.
+        if optim not in self.OPTIMS:
+            raise ValueError('Optim is set %s' % optim)
+        if loss not in self.LOSSES:
+            raise ValueError("<train.py> loss")
+        self.loss_kind, self.optim_kind, self.lr_scheduler = loss, optim, bool(lr_scheduler)
+        self.momentum, self.alpha = 0.9, 0.99               # train.py:288; torch.optim.RMSprop's default
         # topk=(1, 5): the loss of every step also counts the target's top-k hits (the reference's accuracy(), train.py:22-38,
         # :70-72) from the same pass over the logits (ops.kld_sum_loss_and_grad_hits); last_hits / last_logits / accuracy()
         # expose them.  None (the default) issues exactly the launches and captures exactly the graph nodes it did before.
@@ -312,7 +323,7 @@ class DataParallelTrainer:
             if can_split:
                 late_ids = {id(p) for p in model.late_parameters()}
                 params = [p for p in params if id(p) in late_ids] + [p for p in params if id(p) not in late_ids]
-            self.flat = FlatState(params, collect_stack_groups(model))
+            self.flat = FlatState(params, collect_stack_groups(model), self.OPTIMS[optim])
             if can_split:
                 late = [p for p in self.flat.params if id(p) in late_ids]
                 early = [p for p in self.flat.params if id(p) not in late_ids]
@@ -359,7 +370,43 @@ class DataParallelTrainer:
             self.optimizer = None
         else:
             self.grads = FlatGradients(model.parameters())
-            self.optimizer = torch.optim.Adam(self.grads.params, lr=lr)
+            self.optimizer = self._torch_optimizer(self.grads.params, lr)
+
+    # optim -> the flat state buffers it keeps (FlatState)
+    OPTIMS = {"adam": ("m", "v"), "sgd": ("m",), "rms": ("v",)}
+    LOSSES = ("KLD", "BCE", "CE")
+
+    def _torch_optimizer(self, params, lr):
+        """train.py:286-292 (the CPU path's optimizer; on the GPU path the template of optimizer_state_dict's param group)."""
+        if self.optim_kind == "sgd":
+            return torch.optim.SGD(params, lr=lr, momentum=self.momentum)
+        if self.optim_kind == "rms":
+            return torch.optim.RMSprop(params, lr=lr, alpha=self.alpha, eps=self.eps)
+        return torch.optim.Adam(params, lr=lr)
+
+    @classmethod
+    def from_config(cls, model, cf, **kw):
+        """The trainer the reference driver would build from the config module ``cf``, by the defaulting rules of
+        train.py:402-447 and :519-548: ``cf.sgd`` is refused, ``optim`` defaults to adam and ``lr_scheduler`` to on,
+        ``samplingans`` means CE whatever ``loss_metric`` says, otherwise ``loss_metric`` (default KLD) must be BCE or KLD,
+        ``clip_grad`` switches the 0.25 clip, ``lr = cf.lr``.  Keywords override what the config gives."""
+        if hasattr(cf, "sgd"):
+            raise ValueError('sgd has been deprecated. Please use optim')
+        if not hasattr(cf, "lr"):
+            raise AttributeError('lr must be set manually.')
+        sampling = bool(getattr(cf, "samplingans", False))
+        metric = str(cf.loss_metric) if hasattr(cf, "loss_metric") else ("CE" if sampling else "KLD")
+        if sampling:
+            loss = "CE"
+        elif metric in ("BCE", "KLD"):
+            loss = metric
+        else:
+            raise ValueError("<train.py> loss")
+        args = dict(lr=cf.lr, clip=0.25 if getattr(cf, "clip_grad", False) else None, loss=loss,
+                    optim=str(cf.optim) if hasattr(cf, "optim") else "adam",
+                    lr_scheduler=bool(cf.lr_scheduler) if hasattr(cf, "lr_scheduler") else True)
+        args.update(kw)
+        return cls(model, **args)
 
     @staticmethod
     def _model_keys(sample):
@@ -413,9 +460,28 @@ class DataParallelTrainer:
         counts = counts.cpu()
         return tuple(metrics.accuracy(counts[:-1], int(counts[-1]), self.topk))
 
+    def _loss_scale(self, logits):
+        """BCE and CE are MEANS over the global batch in the reference (under DataParallel the criterion sees the gathered
+        outputs), while the gradient all-reduce is a SUM: every rank scales by its local batch x the world size, and the
+        loss it returns is its share of the global loss.  (Fixed at capture for a replayed step; a batch of another size
+        runs through step_eager.)"""
+        B, C = logits.shape
+        return 1.0 / (B * self.world * (C if self.loss_kind == "BCE" else 1))
+
     def _loss_and_grad(self, logits, target):
-        """(loss, dL/dlogits) of the fused KLD kernel -- with topk, its variant that also counts the hits."""
+        """(loss, dL/dlogits) of the fused loss kernel -- with topk, its variant that also counts the hits."""
         from . import ops
+        if self.loss_kind != "KLD":
+            scale = self._loss_scale(logits)
+            # CE: labels outside [0, C) are refused on the host -- except inside a capture, which reads nothing back (the
+            # kernel clamps the index, so a replayed step stays in bounds whatever the labels are)
+            extra = {} if self.loss_kind == "BCE" else {"check": not torch.cuda.is_current_stream_capturing()}
+            fn = "bce_mean_loss_and_grad" if self.loss_kind == "BCE" else "ce_mean_loss_and_grad"
+            if not self.topk:
+                return getattr(ops, fn)(logits, target, scale, **extra)
+            loss, d_logits, hits = getattr(ops, fn + "_hits")(logits, target, self.kmax, scale, **extra)
+            self._front_out = (hits, logits.detach(), logits.size(0))
+            return loss, d_logits
         if self.topk:
             loss, d_logits, hits = ops.kld_sum_loss_and_grad_hits(logits, target, self.kmax)
             self._front_out = (hits, logits.detach(), logits.size(0))
@@ -426,8 +492,39 @@ class DataParallelTrainer:
         """scheduler.step() precedes optimizer.step() in the reference (train.py:75-86): step t uses lr0*gamma^t."""
         self.iteration += 1
         self.adam_steps += 1
-        self._lr = self.base_lr * self.gamma ** self.iteration
+        if self.lr_scheduler:          # (scheduler = None, train.py:295-298: lr stays cf.lr; the iteration still counts)
+            self._lr = self.base_lr * self.gamma ** self.iteration
         return self._lr
+
+    def _cpu_loss(self, logits, target):
+        """torch's own criteria (train.py:519-548), BCE / CE as this rank's share of the mean over the global batch."""
+        if self.loss_kind == "BCE":
+            loss = F.binary_cross_entropy(torch.sigmoid(logits), target)
+        elif self.loss_kind == "CE":
+            loss = F.cross_entropy(logits, target)
+        else:
+            return kld_sum_loss(logits, target)
+        return loss / self.world if self.world > 1 else loss
+
+    def _optimizer_launch(self, lr=None):
+        """The optimizer pass of the GPU tail on the clipped gradients: lr given -> a launch argument (eager steps), None ->
+        read from the step block on the device (replayed steps)."""
+        from . import ops
+        f = self.flat
+        if self.optim_kind == "sgd":
+            if lr is None:
+                ops.sgd_step_dyn(f.p, f.g, f.m, f.norm_and_coef, self.step_scalars, self.momentum)
+            else:
+                ops.sgd_step(f.p, f.g, f.m, f.norm_and_coef, lr, self.momentum)
+        elif self.optim_kind == "rms":
+            if lr is None:
+                ops.rmsprop_step_dyn(f.p, f.g, f.v, f.norm_and_coef, self.step_scalars, self.alpha, self.eps)
+            else:
+                ops.rmsprop_step(f.p, f.g, f.v, f.norm_and_coef, lr, self.alpha, self.eps)
+        elif lr is None:
+            ops.adam_step_dyn(f.p, f.g, f.m, f.v, f.norm_and_coef, self.step_scalars, self.betas[0], self.betas[1], self.eps)
+        else:
+            ops.adam_step(f.p, f.g, f.m, f.v, f.norm_and_coef, lr, self.betas[0], self.betas[1], self.eps, self.adam_steps)
 
     def step_eager(self, sample, target):
         """The same step launched kernel by kernel (no graph replay)."""
@@ -437,10 +534,10 @@ class DataParallelTrainer:
             loss = self._run_phases(sample, target, device_seed=False)
             lr = self._advance_lr()
             ops.grad_norm_clip_coef(f.g, self.clip if self.clip else 0.0, f.norm_and_coef, f.workspace)
-            ops.adam_step(f.p, f.g, f.m, f.v, f.norm_and_coef, lr, self.betas[0], self.betas[1], self.eps, self.adam_steps)
+            self._optimizer_launch(lr)
             return loss, f.norm_and_coef[0]
         logits = self.model(sample)
-        loss = kld_sum_loss(logits, target)
+        loss = self._cpu_loss(logits, target)
         if self.topk:
             from . import metrics
             self._front_out = (metrics.topk_hits(logits, target, self.kmax), logits.detach(), logits.size(0))
@@ -504,11 +601,11 @@ class DataParallelTrainer:
         return loss
 
     def _tail(self):
-        """clip + Adam with the per-step scalars read from device memory (graph 2)."""
+        """clip + the optimizer pass with the per-step scalars read from device memory (graph 2)."""
         from . import ops
         f = self.flat
         ops.grad_norm_clip_coef(f.g, self.clip if self.clip else 0.0, f.norm_and_coef, f.workspace)
-        ops.adam_step_dyn(f.p, f.g, f.m, f.v, f.norm_and_coef, self.step_scalars, self.betas[0], self.betas[1], self.eps)
+        self._optimizer_launch()
 
     def _set_step_scalars(self):
         lr = self._advance_lr()
@@ -519,8 +616,11 @@ class DataParallelTrainer:
         pending = self._ring_events[slot]
         if pending is not None:
             pending.synchronize()
-        self._step_scalars_host[slot, 0] = lr / (1.0 - self.betas[0] ** self.adam_steps)
-        self._step_scalars_host[slot, 1] = 1.0 / (1.0 - self.betas[1] ** self.adam_steps) ** 0.5
+        if self.optim_kind == "adam":
+            self._step_scalars_host[slot, 0] = lr / (1.0 - self.betas[0] ** self.adam_steps)
+            self._step_scalars_host[slot, 1] = 1.0 / (1.0 - self.betas[1] ** self.adam_steps) ** 0.5
+        else:
+            self._step_scalars_host[slot, 0] = lr         # SGD / RMSprop read the learning rate alone (word 0)
         self._seed_host[slot, 0] = int(torch.randint(0, 2 ** 62, (1,), device="cpu").item())   # torch.manual_seed governs it
         self._step_block.copy_(self._step_block_host[slot], non_blocking=True)
         done = torch.cuda.Event()
@@ -697,10 +797,11 @@ class DataParallelTrainer:
         self._lr = self.base_lr
         if self.hip:
             # fills are kernels and the moment buffers keep their addresses: a captured step stays valid
-            self.flat.m.zero_()
-            self.flat.v.zero_()
+            for t in (self.flat.m, self.flat.v):
+                if t is not None:
+                    t.zero_()
         else:
-            self.optimizer = torch.optim.Adam(self.grads.params, lr=self.base_lr)
+            self.optimizer = self._torch_optimizer(self.grads.params, self.base_lr)
 
     def begin_epoch(self, epoch, cf):
         """The optimizer re-creation rule at the top of the reference's epoch loop (train.py:718-721): at
@@ -724,6 +825,21 @@ class DataParallelTrainer:
         where = {id(p): (o, p) for p, o in zip(f.params, f.offsets)}
         params = self._optimizer_params()
         state = {}
+        if self.optim_kind != "adam":
+            # torch.optim.SGD: {momentum_buffer}; torch.optim.RMSprop: {step (a float32 scalar tensor), square_avg}; the param
+            # group is the one this torch version writes for that optimizer (keys and defaults taken from a throw-away instance)
+            if self.adam_steps > 0:
+                for i, p in enumerate(params):
+                    o, _ = where[id(p)]
+                    n = p.numel()
+                    if self.optim_kind == "sgd":
+                        state[i] = {"momentum_buffer": f.m[o:o + n].view_as(p).clone()}
+                    else:
+                        state[i] = {"step": torch.tensor(float(self.adam_steps), dtype=torch.float32),
+                                    "square_avg": f.v[o:o + n].view_as(p).clone()}
+            group = dict(self._torch_optimizer([torch.zeros(1)], self.base_lr).state_dict()["param_groups"][0])
+            group.update(lr=self._lr, initial_lr=self.base_lr, params=list(range(len(params))))
+            return {"state": state, "param_groups": [group]}
         if self.adam_steps > 0:
             for i, p in enumerate(params):
                 o, _ = where[id(p)]
@@ -739,6 +855,9 @@ class DataParallelTrainer:
         """``optimizer.load_state_dict`` (train.py:283).  As in the reference, the scheduler is not part of the
         checkpoint: it was created just before the load (train.py:519,:575) and starts over from ``cf.lr``, while
         Adam's moments and step count continue."""
+        kind = self._state_dict_kind(sd)
+        if kind != self.optim_kind:
+            raise ValueError("loaded state dict belongs to optim = '%s', this trainer runs '%s'" % (kind, self.optim_kind))
         if not self.hip:
             self.optimizer.load_state_dict(sd)
             return
@@ -748,6 +867,9 @@ class DataParallelTrainer:
         group = sd["param_groups"][0]
         if len(sd["param_groups"]) != 1 or len(group["params"]) != len(params):
             raise ValueError("loaded state dict has a different number of parameter groups / parameters")
+        if kind != "adam":
+            self._load_flat_state(sd, group, params, where)
+            return
         self.betas = tuple(group.get("betas", self.betas))
         self.eps = group.get("eps", self.eps)
         steps = set()
@@ -768,6 +890,42 @@ class DataParallelTrainer:
         if len(steps) > 1:
             raise ValueError("per-parameter Adam step counts differ (%s): one fused step count is kept" % sorted(steps))
         self.adam_steps = steps.pop() if steps else 0
+        self.iteration = 0
+        self._lr = self.base_lr
+
+    @staticmethod
+    def _state_dict_kind(sd):
+        """Which of the reference's optimizers wrote this state dict, from the keys only that optimizer's param group has."""
+        group = sd["param_groups"][0]
+        return "adam" if "betas" in group else "rms" if "alpha" in group else "sgd" if "nesterov" in group else "?"
+
+    def _load_flat_state(self, sd, group, params, where):
+        """load_optimizer_state_dict for SGD (momentum_buffer -> FlatState.m) and RMSprop (square_avg -> FlatState.v)."""
+        f = self.flat
+        key_name, buf = ("momentum_buffer", f.m) if self.optim_kind == "sgd" else ("square_avg", f.v)
+        if self.optim_kind == "sgd":
+            self.momentum = group.get("momentum", self.momentum)
+        else:
+            self.alpha, self.eps = group.get("alpha", self.alpha), group.get("eps", self.eps)
+        steps, loaded = set(), 0
+        with torch.no_grad():
+            buf.zero_()
+            for key, p in zip(group["params"], params):
+                st = sd["state"].get(key)
+                if st is None or st.get(key_name) is None:     # (SGD keeps momentum_buffer None before its first step)
+                    continue
+                if tuple(st[key_name].shape) != tuple(p.shape):
+                    raise ValueError("optimizer state of parameter %d has shape %s, expected %s"
+                                     % (key, tuple(st[key_name].shape), tuple(p.shape)))
+                o, n = where[id(p)], p.numel()
+                buf[o:o + n].view_as(p).copy_(st[key_name])
+                loaded += 1
+                if "step" in st:
+                    steps.add(int(st["step"]))
+        if len(steps) > 1:
+            raise ValueError("per-parameter step counts differ (%s): one fused step count is kept" % sorted(steps))
+        # SGD's state carries no step count: any positive one says "the buffers are live" (optimizer_state_dict writes them)
+        self.adam_steps = steps.pop() if steps else (1 if loaded else 0)
         self.iteration = 0
         self._lr = self.base_lr
 
