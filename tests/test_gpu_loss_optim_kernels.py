@@ -1,4 +1,4 @@
-"""Kernel-level checks of the BCE / CE loss kernels (csrc/loss_mean.hip) and the SGD / RMSprop passes
+"""Kernel-level checks of the BCE / CE loss kernels (csrc/loss.hip) and the SGD / RMSprop passes
 (csrc/optimizer_sgd_rms.hip) against torch's own classes in float64 on the CPU, at the sizes where the kernels change path:
 the 256-thread boundaries and the 4096-column register limit of a row, the 256-row stride of the one-workgroup total, the
 float4 / scalar-tail / block boundaries of the flat optimizer pass.
@@ -121,7 +121,7 @@ def test_hits_follow_the_documented_order_and_leave_the_loss_alone(B, C, k):
     for kind, target in (("bce", a), ("ce", labels)):
         plain = getattr(ops, kind + "_mean_loss_and_grad")(zg, target.to(dev()))
         loss, d, hits = getattr(ops, kind + "_mean_loss_and_grad_hits")(zg, target.to(dev()), k)
-        # the restatement of metrics.hip's order on the CPU (tests/test_metrics.py pins it to torch.topk)
+        # the restatement of loss.hip's order on the CPU (tests/test_metrics.py pins it to torch.topk)
         assert hits.dtype == torch.int32 and hits.cpu().tolist() == metrics.topk_hits(z, target, k).tolist(), kind
         # torch.topk itself, on the rows where it has no choice to make: no NaN and the target's logit tied with no other
         t = target if kind == "ce" else a.max(1).indices

@@ -1,4 +1,4 @@
-"""GPU: the accuracy / prediction kernels (csrc/metrics.hip) against metrics.py's CPU restatement (itself held to the
+"""GPU: the accuracy / prediction kernels (csrc/loss.hip) against metrics.py's CPU restatement (itself held to the
 reference's semantics in tests/test_metrics.py), the trainer's topk=(1, 5) against a topk=None twin, and the graph-replayed
 Evaluator against an eager eval forward.  Indices and hit counts must be EXACT; the loss and gradient of the hits variant
 must be the same bits as the plain loss kernel's."""

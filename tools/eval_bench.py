@@ -106,7 +106,7 @@ def main():
     ap.add_argument("--step-block", type=int, default=20)
     ap.add_argument("--skip-step", action="store_true", help="eval throughput only")
     ap.add_argument("--skip-eval", action="store_true", help="the two step forms only (e.g. under rocprofv3 --kernel-trace --stats, "
-                    "which then lists kld_rows_kernel and kld_hits_rows_kernel side by side)")
+                    "which then lists kld_rows_kernel<false> and kld_rows_kernel<true> side by side)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "eval_bench needs a GPU"
     dev = torch.device("cuda:0")

@@ -1,5 +1,5 @@
 """Evaluation of the reference (train.py:110-191, visu.py:188-194): forward in eval mode without autograd, the logits turned
-into answers on the GPU (csrc/metrics.hip), the results written as the reference's JSON records.
+into answers on the GPU (csrc/loss.hip), the results written as the reference's JSON records.
 
     ev = Evaluator(model)                      # graph=True: the forward + predictions replayed as one hipGraph
     results, acc = ev.run(loader, a_vocab, eval_metric="OpenEnded")

@@ -1,7 +1,7 @@
 """What the reference's loops report from the logits: top-k accuracy (train.py:22-38) and the predictions of test()
 (train.py:110-191) and visu.py:188-194.
 
-GPU tensors go through the HIP kernels of csrc/metrics.hip (ops.predict_topk / ops.predict_candidates /
+GPU tensors go through the HIP kernels of csrc/loss.hip (ops.predict_topk / ops.predict_candidates /
 ops.kld_sum_loss_and_grad_hits); CPU tensors (the gloo tests, the CPU trainer) through torch ops with the same semantics.
 
 One order everywhere: NaN ranks above every number (as in torch's topk / sort / max), otherwise the larger value ranks

@@ -1746,24 +1746,66 @@ def embedding(weight, idx, padding_idx=None):
     return EmbeddingFn.apply(weight, idx, padding_idx)
 
 
+def _check_k(what, C, k):
+    if not 1 <= k <= min(16, C):
+        raise ValueError("%s: k=%d outside [1, min(16, C=%d)]" % (what, k, C))
+
+
+_LOSS_NAMES = {"KLD": "kld_sum_loss", "BCE": "bce_mean_loss", "CE": "ce_mean_loss"}
+
+
+def _loss_and_grad(kind, logits, target, scale, kmax, want_grad=True):
+    """The host side of every loss entry point below (csrc/loss.hip): checks, buffers, one launch -> (loss, d_logits or None,
+    hits or None).  kind "KLD" (a sum: scale is None) or "BCE" (both with a [B,C] float target) or "CE" (int64 labels [B]);
+    kmax None, or the number of top-k hit counts wanted from the same pass over the logits."""
+    name = _LOSS_NAMES[kind]
+    mean = kind != "KLD"          # BCE / CE take a scale, and refuse a wrong dtype or empty logits as a ValueError of their own
+    what, dtype = ("labels", torch.int64) if kind == "CE" else ("target", torch.float32)
+    if mean:
+        for w, t, d in (("logits", logits, torch.float32), (what, target, dtype)):
+            if isinstance(t, torch.Tensor) and t.dtype != d:
+                raise ValueError("%s: %s must be %s, got %s" % (name, w, d, t.dtype))
+    lg, target = _prep("logits", logits.detach()), _prep(what, target, (dtype,))
+    if kind == "CE":
+        if lg.dim() != 2 or target.dim() != 1 or target.size(0) != lg.size(0):
+            raise ValueError("%s: logits [B,C] and int64 labels [B] expected, got %s and %s" % (name, tuple(lg.shape), tuple(target.shape)))
+    elif lg.dim() != 2 or target.shape != lg.shape:
+        raise ValueError("%s: logits and target must both be [B,C], got %s and %s" % (name, tuple(lg.shape), tuple(target.shape)))
+    B, C = lg.shape
+    args = []
+    if mean:
+        if B == 0 or C == 0:
+            raise ValueError("%s: empty logits %s" % (name, tuple(lg.shape)))
+        scale = float(scale)
+        if not 0.0 < scale < float("inf"):
+            raise ValueError("%s: scale=%r must be positive and finite" % (name, scale))
+        args = [scale]
+    lib = _lib.lib()
+    family = "vqa_mean_loss" if mean else "vqa_kld_sum_loss"
+    hits, shape = None, (B, C, want_grad)
+    if kmax is None:
+        nbytes = getattr(lib, family + "_workspace_bytes")(B)
+    else:
+        kmax, name = int(kmax), name + "_hits"
+        _check_k(name, C, kmax)
+        hits, shape = torch.empty(kmax, device=lg.device, dtype=torch.int32), (B, C, kmax)
+        nbytes = getattr(lib, family + "_hits_workspace_bytes")(B, kmax)
+        args = [_p(hits), kmax] + args
+    loss = torch.empty((), device=lg.device, dtype=torch.float32)
+    d_logits = torch.empty_like(lg) if want_grad else None
+    ws = torch.empty(nbytes // 4, device=lg.device, dtype=torch.float32)
+    _launch(name, shape, getattr(lib, "vqa_" + name), _p(lg), _p(target), _p(loss), _p(d_logits), *args, _p(ws), nbytes, B, C)
+    return loss, d_logits, hits
+
+
 class KldSumLoss(torch.autograd.Function):
     """KLDivLoss(size_average=False)(log_softmax(logits), target) (train.py:536-544) with its gradient from the same
     pass over the logits; the B row losses are added in a fixed order (no atomics, no memset: replays cleanly)."""
 
     @staticmethod
     def forward(ctx, logits, target):
-        logits, target = _prep("logits", logits), _prep("target", target)
-        if logits.dim() != 2 or target.shape != logits.shape:
-            raise ValueError("kld_sum_loss: logits and target must both be [B,C], got %s and %s"
-                             % (tuple(logits.shape), tuple(target.shape)))
-        B, C = logits.shape
-        loss = torch.empty((), device=logits.device, dtype=torch.float32)
-        need = ctx.needs_input_grad[0]
-        d_logits = torch.empty_like(logits) if need else None
-        ws = torch.empty(B, device=logits.device, dtype=torch.float32)
-        _launch("kld_sum_loss", (B, C, need), _lib.lib().vqa_kld_sum_loss, _p(logits), _p(target), _p(loss), _p(d_logits),
-                _p(ws), 4 * B, B, C)
-        if need:
+        loss, d_logits, _ = _loss_and_grad("KLD", logits, target, None, None, want_grad=ctx.needs_input_grad[0])
+        if d_logits is not None:
             ctx.save_for_backward(d_logits)
         return loss
 
@@ -1773,90 +1815,22 @@ class KldSumLoss(torch.autograd.Function):
         return d_logits * g, None
 
 
-def kld_sum_loss_and_grad(logits, target):
-    """(loss, dL/dlogits) of the KLD-sum loss from ONE pass, outside autograd: a train step that backpropagates from the
-    logits with this gradient (``torch.autograd.backward(logits, d_logits)``) skips the loss node's multiply by the
-    incoming scalar 1."""
-    lg, target = _prep("logits", logits.detach()), _prep("target", target)
-    if lg.dim() != 2 or target.shape != lg.shape:
-        raise ValueError("kld_sum_loss: logits and target must both be [B,C], got %s and %s" % (tuple(lg.shape), tuple(target.shape)))
-    B, C = lg.shape
-    loss = torch.empty((), device=lg.device, dtype=torch.float32)
-    d_logits = torch.empty_like(lg)
-    ws = torch.empty(B, device=lg.device, dtype=torch.float32)
-    _launch("kld_sum_loss", (B, C, True), _lib.lib().vqa_kld_sum_loss, _p(lg), _p(target), _p(loss), _p(d_logits), _p(ws), 4 * B, B, C)
-    return loss, d_logits
-
-
 def kld_sum_loss(logits, target):
     return KldSumLoss.apply(logits, target)
 
 
-def _check_k(what, C, k):
-    if not 1 <= k <= min(16, C):
-        raise ValueError("%s: k=%d outside [1, min(16, C=%d)]" % (what, k, C))
+def kld_sum_loss_and_grad(logits, target):
+    """(loss, dL/dlogits) of the KLD-sum loss from ONE pass, outside autograd: a train step that backpropagates from the
+    logits with this gradient (``torch.autograd.backward(logits, d_logits)``) skips the loss node's multiply by the
+    incoming scalar 1."""
+    return _loss_and_grad("KLD", logits, target, None, None)[:2]
 
 
 def kld_sum_loss_and_grad_hits(logits, target, kmax):
     """kld_sum_loss_and_grad plus the target's top-k hits from the same pass over the logits: (loss, d_logits, hits) with
     hits int32[kmax], hits[j] = rows whose target (first index of the row's largest target value) ranks <= j among the
     logits.  loss and d_logits are bitwise those of kld_sum_loss_and_grad."""
-    lg, target = _prep("logits", logits.detach()), _prep("target", target)
-    if lg.dim() != 2 or target.shape != lg.shape:
-        raise ValueError("kld_sum_loss: logits and target must both be [B,C], got %s and %s" % (tuple(lg.shape), tuple(target.shape)))
-    B, C = lg.shape
-    kmax = int(kmax)
-    _check_k("kld_sum_loss_hits", C, kmax)
-    loss = torch.empty((), device=lg.device, dtype=torch.float32)
-    d_logits = torch.empty_like(lg)
-    hits = torch.empty(kmax, device=lg.device, dtype=torch.int32)
-    nbytes = _lib.lib().vqa_kld_sum_loss_hits_workspace_bytes(B, kmax)
-    ws = torch.empty(nbytes // 4, device=lg.device, dtype=torch.float32)
-    _launch("kld_sum_loss_hits", (B, C, kmax), _lib.lib().vqa_kld_sum_loss_hits, _p(lg), _p(target), _p(loss), _p(d_logits),
-            _p(hits), kmax, _p(ws), nbytes, B, C)
-    return loss, d_logits, hits
-
-
-def _mean_loss(kind, logits, target, scale, kmax):
-    """The shared body of the BCE / CE wrappers below: checks, buffers, one launch -> (loss, d_logits, hits or None)."""
-    name = kind + "_mean_loss"
-    for what, t, dtype in (("logits", logits, torch.float32), ("target", target, torch.float32) if kind == "bce" else
-                           ("labels", target, torch.int64)):
-        if isinstance(t, torch.Tensor) and t.dtype != dtype:
-            raise ValueError("%s: %s must be %s, got %s" % (name, what, dtype, t.dtype))
-    lg = _prep("logits", logits.detach())
-    if kind == "bce":
-        target = _prep("target", target)
-        if lg.dim() != 2 or target.shape != lg.shape:
-            raise ValueError("%s: logits and target must both be [B,C], got %s and %s" % (name, tuple(lg.shape), tuple(target.shape)))
-    else:
-        target = _prep("labels", target, (torch.int64,))
-        if lg.dim() != 2 or target.dim() != 1 or target.size(0) != lg.size(0):
-            raise ValueError("%s: logits [B,C] and int64 labels [B] expected, got %s and %s"
-                             % (name, tuple(lg.shape), tuple(target.shape)))
-    B, C = lg.shape
-    if B == 0 or C == 0:
-        raise ValueError("%s: empty logits %s" % (name, tuple(lg.shape)))
-    scale = float(scale)
-    if not 0.0 < scale < float("inf"):
-        raise ValueError("%s: scale=%r must be positive and finite" % (name, scale))
-    lib = _lib.lib()
-    loss = torch.empty((), device=lg.device, dtype=torch.float32)
-    d_logits = torch.empty_like(lg)
-    if kmax is None:
-        nbytes = lib.vqa_mean_loss_workspace_bytes(B)
-        ws = torch.empty(nbytes // 4, device=lg.device, dtype=torch.float32)
-        _launch(name, (B, C, True), getattr(lib, "vqa_" + name), _p(lg), _p(target), _p(loss), _p(d_logits), scale, _p(ws), nbytes,
-                B, C)
-        return loss, d_logits, None
-    kmax = int(kmax)
-    _check_k(name + "_hits", C, kmax)
-    hits = torch.empty(kmax, device=lg.device, dtype=torch.int32)
-    nbytes = lib.vqa_mean_loss_hits_workspace_bytes(B, kmax)
-    ws = torch.empty(nbytes // 4, device=lg.device, dtype=torch.float32)
-    _launch(name + "_hits", (B, C, kmax), getattr(lib, "vqa_" + name + "_hits"), _p(lg), _p(target), _p(loss), _p(d_logits),
-            _p(hits), kmax, scale, _p(ws), nbytes, B, C)
-    return loss, d_logits, hits
+    return _loss_and_grad("KLD", logits, target, None, kmax)
 
 
 def check_labels(labels, C):
@@ -1866,34 +1840,38 @@ def check_labels(labels, C):
         raise ValueError("ce_mean_loss: labels must lie in [0, C=%d), got min %d max %d" % (C, int(labels.min()), int(labels.max())))
 
 
+def check_ce_labels(logits, labels):
+    """check_labels for the labels of a CE call -- where they are what the kernel takes (int64 against [B,C] logits); anything
+    else is left to the wrapper's own dtype and shape errors."""
+    if isinstance(labels, torch.Tensor) and labels.dtype == torch.int64 and logits.dim() == 2:
+        check_labels(labels, logits.size(1))
+
+
 def bce_mean_loss_and_grad(logits, target, scale=None):
     """(loss, dL/dlogits) of nn.BCELoss()(sigmoid(logits), target) (train.py:522-534) from ONE pass, outside autograd, in
     the stable softplus form.  ``scale`` defaults to 1 / (B * C), the mean over this batch; a data-parallel rank passes
     1 / (B_global * C) so that the summed gradients are the global mean's."""
-    B, C = logits.shape[0], logits.shape[-1]
-    return _mean_loss("bce", logits, target, 1.0 / max(B * C, 1) if scale is None else scale, None)[:2]
+    return bce_mean_loss_and_grad_hits(logits, target, None, scale)[:2]
 
 
 def bce_mean_loss_and_grad_hits(logits, target, kmax, scale=None):
     """bce_mean_loss_and_grad (bitwise the same loss and d_logits) plus hits int32[kmax] as kld_sum_loss_and_grad_hits counts them."""
     B, C = logits.shape[0], logits.shape[-1]
-    return _mean_loss("bce", logits, target, 1.0 / max(B * C, 1) if scale is None else scale, kmax)
+    return _loss_and_grad("BCE", logits, target, 1.0 / max(B * C, 1) if scale is None else scale, kmax)
 
 
 def ce_mean_loss_and_grad(logits, labels, scale=None, check=True):
     """(loss, dL/dlogits) of nn.CrossEntropyLoss()(logits, labels) (train.py:519-520) from ONE pass, outside autograd; labels
     int64 [B].  ``scale`` defaults to 1 / B.  check=False skips the host-side range check of the labels (under graph capture,
     where nothing may be read back; the kernel clamps the index)."""
-    if check and isinstance(labels, torch.Tensor) and labels.dtype == torch.int64 and logits.dim() == 2:
-        check_labels(labels, logits.size(1))
-    return _mean_loss("ce", logits, labels, 1.0 / max(logits.shape[0], 1) if scale is None else scale, None)[:2]
+    return ce_mean_loss_and_grad_hits(logits, labels, None, scale, check)[:2]
 
 
 def ce_mean_loss_and_grad_hits(logits, labels, kmax, scale=None, check=True):
     """ce_mean_loss_and_grad (bitwise the same loss and d_logits) plus hits int32[kmax]: hits[j] = rows whose label ranks <= j."""
-    if check and isinstance(labels, torch.Tensor) and labels.dtype == torch.int64 and logits.dim() == 2:
-        check_labels(labels, logits.size(1))
-    return _mean_loss("ce", logits, labels, 1.0 / max(logits.shape[0], 1) if scale is None else scale, kmax)
+    if check:
+        check_ce_labels(logits, labels)
+    return _loss_and_grad("CE", logits, labels, 1.0 / max(logits.shape[0], 1) if scale is None else scale, kmax)
 
 
 def predict_topk(logits, k, target=None, probs=True):

@@ -471,22 +471,16 @@ class DataParallelTrainer:
     def _loss_and_grad(self, logits, target):
         """(loss, dL/dlogits) of the fused loss kernel -- with topk, its variant that also counts the hits."""
         from . import ops
-        if self.loss_kind != "KLD":
-            scale = self._loss_scale(logits)
-            # CE: labels outside [0, C) are refused on the host -- except inside a capture, which reads nothing back (the
-            # kernel clamps the index, so a replayed step stays in bounds whatever the labels are)
-            extra = {} if self.loss_kind == "BCE" else {"check": not torch.cuda.is_current_stream_capturing()}
-            fn = "bce_mean_loss_and_grad" if self.loss_kind == "BCE" else "ce_mean_loss_and_grad"
-            if not self.topk:
-                return getattr(ops, fn)(logits, target, scale, **extra)
-            loss, d_logits, hits = getattr(ops, fn + "_hits")(logits, target, self.kmax, scale, **extra)
+        # CE: labels outside [0, C) are refused on the host -- except inside a capture, which reads nothing back (the
+        # kernel clamps the index, so a replayed step stays in bounds whatever the labels are)
+        if self.loss_kind == "CE" and not torch.cuda.is_current_stream_capturing():
+            ops.check_ce_labels(logits, target)
+        loss, d_logits, hits = ops._loss_and_grad(self.loss_kind, logits, target,
+                                                  None if self.loss_kind == "KLD" else self._loss_scale(logits),
+                                                  self.kmax if self.topk else None)
+        if hits is not None:
             self._front_out = (hits, logits.detach(), logits.size(0))
-            return loss, d_logits
-        if self.topk:
-            loss, d_logits, hits = ops.kld_sum_loss_and_grad_hits(logits, target, self.kmax)
-            self._front_out = (hits, logits.detach(), logits.size(0))
-            return loss, d_logits
-        return ops.kld_sum_loss_and_grad(logits, target)
+        return loss, d_logits
 
     def _advance_lr(self):
         """scheduler.step() precedes optimizer.step() in the reference (train.py:75-86): step t uses lr0*gamma^t."""
