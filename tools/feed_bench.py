@@ -31,6 +31,9 @@ def main():
                     "long the trainer's thread may keep the GIL while the producer thread waits for it")
     ap.add_argument("--transport", choices=["f32", "bf16"], default="f32",
                     help="bf16: the regions cross PCIe as bf16 (half the bytes) and are widened on the device (ops.widen_bf16); the step is the fp32 one")
+    ap.add_argument("--answers", choices=["dense", "sparse"], default="dense",
+                    help="sparse: the answers cross as (id, probability) pairs (a_idx / a_val [B,K]) and the loss is computed from them; "
+                         "no dense [B,2000] target is built, copied or read")
     args = ap.parse_args()
     if args.switch_interval > 0:
         sys.setswitchinterval(args.switch_interval)
@@ -40,6 +43,14 @@ def main():
     vdt = torch.bfloat16 if args.transport == "bf16" else torch.float32
     host = [{"v": torch.randn(B, 36, 2048).to(vdt).pin_memory(), "q_idxes": torch.randn(B, 2400).pin_memory(),
              "a": torch.softmax(torch.randn(B, 2000), 1).pin_memory()} for _ in range(3)]
+    akeys = ("a",)
+    if args.answers == "sparse":
+        akeys = ("a_idx", "a_val")
+        for h in host:
+            del h["a"]
+            h["a_idx"] = torch.stack([torch.randperm(2000)[:10] for _ in range(B)]).to(torch.int32).pin_memory()
+            h["a_val"] = torch.softmax(torch.randn(B, 10), 1).pin_memory()
+    target = (lambda b: b["a"]) if args.answers == "dense" else (lambda b: {"a_idx": b["a_idx"], "a_val": b["a_val"]})
     store = qa = None
     if args.store:
         import numpy as np
@@ -65,13 +76,14 @@ def main():
     def stream(n):
         if store is not None:        # the reference loader's batches from the memory-mapped store (question vectors stand in for ids)
             loader = feed.store_batches(store, qa, B, 2000, shuffle=True, seed=0, pin=True, region_dtype=vdt, ring=args.depth + 2 * args.producers + 2,
-                                        q_dtype=torch.float32, prefetch=2 * args.producers, epochs=None, producers=args.producers)
+                                        q_dtype=torch.float32, prefetch=2 * args.producers, epochs=None, producers=args.producers,
+                                        answers=args.answers)
             waited = 0.0
             for _ in range(n):
                 t_w = time.perf_counter()
                 b = next(loader)
                 waited += time.perf_counter() - t_w
-                yield {"v": b["v"], "q_idxes": b["q_idxes"], "a": b["a"]}
+                yield dict({"v": b["v"], "q_idxes": b["q_idxes"]}, **{k: b[k] for k in akeys})
             loader.close()
             stats["producer_wait_ms_per_batch"] = 1e3 * waited / max(n, 1)
             return
@@ -81,13 +93,13 @@ def main():
     pre = feed.DevicePrefetcher(stream(4 + 2 * args.depth), dev, depth=args.depth)
     slots = []
     for b in pre:                                         # warm-up + graph capture (one graph per device slot, each replayed once)
-        tr.step({"v": b["v"], "q_idxes": b["q_idxes"]}, b["a"])
+        tr.step({"v": b["v"], "q_idxes": b["q_idxes"]}, target(b))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     # (the timed stream goes through the SAME prefetcher object's device slots: a fresh one would allocate new slots, i.e. new graphs)
     pre.it = iter(stream(args.steps))
     for b in pre:
-        tr.step({"v": b["v"], "q_idxes": b["q_idxes"]}, b["a"])
+        tr.step({"v": b["v"], "q_idxes": b["q_idxes"]}, target(b))
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if stats:
@@ -100,8 +112,8 @@ def main():
         d.copy_(host[0]["v"], non_blocking=True)
     torch.cuda.synchronize()
     h2d = 10 * host[0]["v"].numel() * host[0]["v"].element_size() / (time.perf_counter() - t1) / 1e9
-    print("host-fed (%s transport, %s%s): %.1f samples/s (%.3f ms/step, graph=%s); pinned H2D of v alone: %.1f GB/s"
-          % (args.transport, "copied into the graph's buffers" if args.copy else "%d slots read in place" % args.depth,
+    print("host-fed (%s transport, %s answers, %s%s): %.1f samples/s (%.3f ms/step, graph=%s); pinned H2D of v alone: %.1f GB/s"
+          % (args.transport, args.answers, "copied into the graph's buffers" if args.copy else "%d slots read in place" % args.depth,
              ", FeatureStore of %d images, %d gather threads" % (args.store, args.workers) if args.store else "", B * args.steps / dt, 1e3 * dt / args.steps, tr._graph is not None, h2d))
 
 

@@ -46,12 +46,13 @@ def main():
             st.gather(idx, out)
             ts.append(1e3 * (time.perf_counter() - t))
         print("gather %-8s ms per call: %s" % (str(dt).split(".")[1], " ".join("%.1f" % x for x in ts)))
-        ts = []
-        t = time.perf_counter()
-        for b in feed.store_batches(st, table, B, 2000, pin=pin, region_dtype=dt, q_dtype=torch.float32, ring=3):
-            ts.append(1e3 * (time.perf_counter() - t))
+        for answers in ("dense", "sparse"):
+            ts = []
             t = time.perf_counter()
-        print("store_batches %-8s ms per batch: %s" % (str(dt).split(".")[1], " ".join("%.1f" % x for x in ts)))
+            for b in feed.store_batches(st, table, B, 2000, pin=pin, region_dtype=dt, q_dtype=torch.float32, ring=3, answers=answers):
+                ts.append(1e3 * (time.perf_counter() - t))
+                t = time.perf_counter()
+            print("store_batches %-8s %-6s answers, ms per batch: %s" % (str(dt).split(".")[1], answers, " ".join("%.1f" % x for x in ts)))
 
 
 if __name__ == "__main__":

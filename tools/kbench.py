@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark of libvqa_mi355x.so at the BASELINE shapes (B=512, N=36, D=2048, L=310, H=510, G=4, R=2).
 Interleaved rounds in ONE process (guide rule 24); prints median / min per variant and the roofline fraction.
 
-    python tools/kbench.py [--only k4fwd,k4bwd,k1,k2,k3,k3a,k5,optim,loss | bf16 | head] [--tiles 128x128,64x64] [--rounds 20]
+    python tools/kbench.py [--only k4fwd,k4bwd,k1,k2,k3,k3a,k5,optim,loss,loss_sparse | bf16 | head] [--tiles 128x128,64x64] [--rounds 20]
 """
 import argparse
 import os
@@ -287,6 +287,26 @@ def main():
             report("loss + gradient [%d,%d] (rows + total; includes the wrapper's allocations): 3 arrays" % (B, C),
                    {k: res[k] for k in ("kld", "kld + hits", "bce", "bce + hits")}, 3 * B * C * 4, "GB")
             report("loss + gradient [%d,%d]: 2 arrays" % (B, C), {k: res[k] for k in ("ce", "ce + hits")}, 2 * B * C * 4, "GB")
+    if want("loss_sparse"):
+        # the same criteria from the feed's pairs (csrc/loss_sparse.hip), K = 10 pairs a row, next to the dense kernels on the densified
+        # target in the same run: the sparse kernels read z and write dz (2 arrays, + 8 * K bytes of pairs per row)
+        for C in (2000, 3000):
+            K = 10
+            z = torch.randn(B, C, device=dev) * 4
+            a_idx = torch.stack([torch.randperm(C, device=dev)[:K] for _ in range(B)]).to(torch.int32)
+            a_val = torch.softmax(torch.randn(B, K, device=dev), 1)
+            a = ops.densify(a_idx, a_val, C)
+            res = timeit({"kld dense": lambda: ops.kld_sum_loss_and_grad(z, a), "bce dense": lambda: ops.bce_mean_loss_and_grad(z, a),
+                          "kld sparse": lambda: ops.kld_sum_loss_and_grad_sparse(z, a_idx, a_val),
+                          "kld sparse + hits": lambda: ops.kld_sum_loss_and_grad_sparse_hits(z, a_idx, a_val, 5),
+                          "bce sparse": lambda: ops.bce_mean_loss_and_grad_sparse(z, a_idx, a_val),
+                          "bce sparse + hits": lambda: ops.bce_mean_loss_and_grad_sparse_hits(z, a_idx, a_val, 5),
+                          "ce sampled": lambda: ops.ce_mean_loss_and_grad_sampled(z, a_idx, a_val, seed=1),
+                          "ce sampled + hits": lambda: ops.ce_mean_loss_and_grad_sampled_hits(z, a_idx, a_val, 5, seed=1)}, args.rounds)
+            report("loss + gradient [%d,%d], dense target: 3 arrays" % (B, C), {k: res[k] for k in ("kld dense", "bce dense")},
+                   3 * B * C * 4, "GB")
+            report("loss + gradient [%d,%d], %d pairs a row: 2 arrays + pairs" % (B, C, K),
+                   {k: res[k] for k in res if "dense" not in k}, 2 * B * C * 4 + 8 * B * K, "GB")
     if want("copy"):
         y = torch.empty_like(v)
         fns = {"torch copy 151MB": lambda: y.copy_(v)}

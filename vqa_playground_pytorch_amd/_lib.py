@@ -162,6 +162,15 @@ SIGNATURES = {
     "vqa_bce_mean_loss_hits": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_fl, _c_f, _c_sz, _c_i, _c_i, _c_st]),
     "vqa_ce_mean_loss": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_fl, _c_f, _c_sz, _c_i, _c_i, _c_st]),
     "vqa_ce_mean_loss_hits": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_fl, _c_f, _c_sz, _c_i, _c_i, _c_st]),
+    "vqa_sparse_loss_workspace_bytes": (_c_sz, [_c_i, _c_i]),
+    "vqa_kld_sum_loss_sparse": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_sz, _c_i, _c_i, _c_i, _c_st]),
+    "vqa_kld_sum_loss_sparse_hits": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_f, _c_sz, _c_i, _c_i, _c_i, _c_st]),
+    "vqa_bce_mean_loss_sparse": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_fl, _c_f, _c_sz, _c_i, _c_i, _c_i, _c_st]),
+    "vqa_bce_mean_loss_sparse_hits": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_fl, _c_f, _c_sz, _c_i, _c_i, _c_i, _c_st]),
+    "vqa_ce_mean_loss_sampled": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_fl, _c_u64, _c_f, _c_u64, _c_f, _c_sz,
+                                        _c_i, _c_i, _c_i, _c_st]),
+    "vqa_ce_mean_loss_sampled_hits": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_fl, _c_u64, _c_f, _c_u64, _c_f, _c_sz,
+                                             _c_i, _c_i, _c_i, _c_st]),
     "vqa_grad_norm_workspace_bytes": (_c_sz, []),
     "vqa_grad_norm_clip_coef": (_c_i, [_c_f, _c_sz, _c_fl, _c_f, _c_f, _c_sz, _c_st]),
     "vqa_adam_step": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_sz, _c_f, _c_fl, _c_fl, _c_fl, _c_fl, _c_i, _c_st]),

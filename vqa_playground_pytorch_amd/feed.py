@@ -34,11 +34,28 @@ def soft_target(a_10_idx, num_ans, out=None):
 
 
 MC_CANDIDATES = 50
+MAX_PAIRS = 16         # (answer id, probability) pairs per question a sparse answer target holds (the loss kernels' limit)
 
 
-def collate(items, num_ans, pin=False):
+def _check_answers(answers):
+    if answers not in ("dense", "sparse"):
+        raise ValueError("answers=%r: 'dense' or 'sparse'" % (answers,))
+    return answers == "sparse"
+
+
+def _pair_width(most):
+    """K of a sparse answer target whose longest pair list has `most` entries."""
+    if most > MAX_PAIRS:
+        raise ValueError("a question with %d (answer id, probability) pairs: a sparse answer target holds at most %d" % (most, MAX_PAIRS))
+    return max(1, int(most))
+
+
+def collate(items, num_ans, pin=False, answers="dense"):
     """List of reference-style items {'v' [36,2048], 'q_idxes' [T], 'q_id', 'a_10_idx' or 'a', optionally 'a_mc_idx'} -> one batch dict of
-    contiguous host tensors (optionally pinned), the layout Model.forward and the trainer expect."""
+    contiguous host tensors (optionally pinned), the layout Model.forward and the trainer expect.  answers="sparse": instead of the
+    dense 'a' [B,num_ans] the pairs of 'a_10_idx' as they are, in record order -- 'a_idx' int32 [B,K] and 'a_val' float32 [B,K], K the
+    batch's largest pair count, shorter rows padded with -1 / 0 (ops.densify defines the format; the trainer takes the two keys)."""
+    sparse = _check_answers(answers)
     B = len(items)
     v0 = torch.as_tensor(items[0]["v"])
     mk = (lambda *s, dtype: torch.empty(*s, dtype=dtype).pin_memory()) if pin else (lambda *s, dtype: torch.empty(*s, dtype=dtype))
@@ -46,6 +63,19 @@ def collate(items, num_ans, pin=False):
              "q_idxes": mk(B, len(items[0]["q_idxes"]), dtype=torch.long),
              "q_id": torch.tensor([int(it.get("q_id", i)) for i, it in enumerate(items)], dtype=torch.long)}
     has_a = "a" in items[0] or "a_10_idx" in items[0]
+    if sparse and has_a:
+        if any("a_10_idx" not in it for it in items):
+            raise ValueError("answers='sparse' needs every item's 'a_10_idx' pairs: a dense 'a' cannot be served sparse")
+        K = _pair_width(max(len(it["a_10_idx"]) for it in items))
+        batch["a_idx"], batch["a_val"] = mk(B, K, dtype=torch.int32), mk(B, K, dtype=torch.float32)
+        batch["a_idx"].fill_(-1)
+        batch["a_val"].zero_()
+        for i, it in enumerate(items):
+            for j, (c_id, c_prob) in enumerate(it["a_10_idx"]):
+                if not 0 <= int(c_id) < num_ans:
+                    raise IndexError("collate: answer id outside [0, %d)" % num_ans)
+                batch["a_idx"][i, j], batch["a_val"][i, j] = int(c_id), float(c_prob)
+        has_a = False
     if has_a:
         batch["a"] = mk(B, num_ans, dtype=torch.float32)
     if "a_mc_idx" in items[0]:
@@ -266,7 +296,7 @@ class _QaTable:
     DataLoader workers): feature rows, the question matrix, ids, and the soft answers as CSR (datasets.py:963-969: a[c_id] = c_prob,
     the last pair of a duplicated id wins)."""
 
-    def __init__(self, store, qa_items, num_ans, q_dtype):
+    def __init__(self, store, qa_items, num_ans, q_dtype, require_answers=False):
         n = len(qa_items)
         self.rows = np.fromiter((it["v_idx"] if "v_idx" in it else store.index(it["img_filename"]) for it in qa_items), np.int64, n)
         self.q_ids = np.fromiter((int(it.get("q_id", i)) for i, it in enumerate(qa_items)), np.int64, n)
@@ -277,6 +307,11 @@ class _QaTable:
             self.a = np.asarray([np.asarray(it["a"], dtype=np.float32) for it in qa_items])
         elif self.kind == "soft":
             counts = np.fromiter((len(it["a_10_idx"]) for it in qa_items), np.int64, n)
+            if require_answers and n and counts.min() == 0:
+                i = int(np.argmin(counts))                         # the reference: assert item_vqa['a_10_idx'] (datasets.py:953, :962)
+                raise ValueError("record %d (q_id %s) has an empty 'a_10_idx': a training record needs at least one answer pair"
+                                 % (i, qa_items[i].get("q_id", i)))
+            self.max_pairs = int(counts.max()) if n else 0
             self.ptr = np.concatenate([[0], np.cumsum(counts)])
             flat = [pair for it in qa_items for pair in it["a_10_idx"]]
             self.cols = np.fromiter((int(c) for c, _ in flat), np.int64, len(flat))
@@ -297,14 +332,42 @@ class _QaTable:
             src = np.concatenate([np.arange(x, y) for x, y in zip(lo, hi)]) if len(ids) else np.zeros(0, np.int64)
             dst[rows, self.cols[src]] = self.vals[src]        # (in order: the last pair of a duplicated id wins, as in the reference's loop)
 
+    def pair_width(self):
+        """K of the sparse answer target this table serves (its largest pair count); ValueError when it cannot serve one."""
+        if self.kind != "soft":
+            raise ValueError("answers='sparse' needs records with 'a_10_idx' pairs: a dense 'a' cannot be served sparse")
+        return _pair_width(self.max_pairs)
 
-def qa_table(store, qa_items, num_ans, q_dtype=torch.long):
-    """The array form of the per-question records that store_batches works on; build it once, pass it instead of the list."""
-    return _QaTable(store, qa_items, num_ans, q_dtype)
+    def padded_pairs(self):
+        """The CSR as two padded arrays [n,K] (ids int32, -1 where a row has no pair; values float32, 0 there), built once: a
+        batch's sparse target is then two row gathers."""
+        if getattr(self, "_pairs", None) is None:
+            K, n = self.pair_width(), len(self.rows)
+            counts = np.diff(self.ptr)
+            rows = np.repeat(np.arange(n), counts)
+            within = np.arange(len(self.cols)) - np.repeat(self.ptr[:-1], counts)
+            pidx, pval = np.full((n, K), -1, np.int32), np.zeros((n, K), np.float32)
+            pidx[rows, within] = self.cols
+            pval[rows, within] = self.vals
+            self._pairs = (pidx, pval)
+        return self._pairs
+
+    def fill_pairs(self, a_idx, a_val, ids):
+        """The pairs of records `ids` as they are, in record order, into a_idx int32 / a_val float32 [b,K]; padding -1 / 0."""
+        pidx, pval = self.padded_pairs()
+        a_idx.numpy()[...] = pidx[ids]
+        a_val.numpy()[...] = pval[ids]
+
+
+def qa_table(store, qa_items, num_ans, q_dtype=torch.long, require_answers=False):
+    """The array form of the per-question records that store_batches works on; build it once, pass it instead of the list.
+    require_answers=True: a record with an empty 'a_10_idx' raises ValueError naming it (the reference's training loader asserts the
+    same per item, datasets.py:953, :962)."""
+    return _QaTable(store, qa_items, num_ans, q_dtype, require_answers)
 
 
 def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, pin=True, region_dtype=torch.float32, ring=3,
-                  q_dtype=torch.long, prefetch=0, epochs=1, producers=1):
+                  q_dtype=torch.long, prefetch=0, epochs=1, producers=1, answers="dense"):
     """The reference's loader (datasets.py:893-977: `Inner.__getitem__` + DataLoader(batch_size, shuffle, pin_memory=True), no
     drop_last) over a FeatureStore: yields batch dicts {'v' [B,N,D], 'q_idxes' [B,T], 'q_id' [B], 'a' [B,num_ans]} of host tensors.
     qa_items: the reference's per-question records -- 'img_filename' (or 'v_idx'), 'q_idxes', 'q_id', 'a_10_idx' [(answer id,
@@ -318,7 +381,11 @@ def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, p
     release the GIL in the copies that dominate); producers > 1: that many threads, each assembling whole batches, delivered in
     order.  epochs: passes over the records (None: for ever), each with its own shuffle
     (seed + epoch) -- ONE generator for a whole run keeps its pinned staging ring (page-locking 160 MB per slot takes tens of
-    milliseconds: a generator per epoch would pay that again every time)."""
+    milliseconds: a generator per epoch would pay that again every time).  answers="sparse": instead of 'a' the batches carry the pairs
+    as they are, 'a_idx' int32 [B,K] and 'a_val' float32 [B,K] in the same staging ring (K = the table's largest pair count, at most
+    16; shorter rows padded with -1 / 0, pairs in record order): no dense [B,num_ans] row is allocated, filled or copied, the
+    trainer computes its loss from the pairs (ops.densify defines the format).  Records given with a dense 'a' cannot be served sparse."""
+    sparse = _check_answers(answers)
     n = len(qa_items.rows) if isinstance(qa_items, _QaTable) else len(qa_items)
 
     def order_of(epoch):
@@ -329,6 +396,7 @@ def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, p
     table = qa_items if isinstance(qa_items, _QaTable) else _QaTable(store, qa_items, num_ans, q_dtype)
     T = table.q.shape[1]
     has_a = table.kind is not None
+    K = table.padded_pairs()[0].shape[1] if sparse and has_a else 0       # (built here, before any producer thread runs)
     mk = (lambda *s, dtype: torch.empty(*s, dtype=dtype).pin_memory()) if pin else (lambda *s, dtype: torch.empty(*s, dtype=dtype))
     slots = []
 
@@ -341,11 +409,16 @@ def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, p
         with slot_lock:
             while len(slots) <= k:
                 slots.append({"v": mk(batch_size, *store.sample_shape, dtype=region_dtype), "q_idxes": mk(batch_size, T, dtype=q_dtype),
-                              "a": mk(batch_size, num_ans, dtype=torch.float32) if has_a else None})
+                              "a": mk(batch_size, num_ans, dtype=torch.float32) if has_a and not sparse else None,
+                              "a_idx": mk(batch_size, K, dtype=torch.int32) if K else None,
+                              "a_val": mk(batch_size, K, dtype=torch.float32) if K else None})
         s = slots[k]
         batch = {"v": store.gather(table.rows[ids], s["v"]), "q_idxes": s["q_idxes"][:b], "q_id": torch.from_numpy(table.q_ids[ids])}
         batch["q_idxes"].numpy()[...] = table.q[ids]
-        if has_a:
+        if K:
+            batch["a_idx"], batch["a_val"] = s["a_idx"][:b], s["a_val"][:b]
+            table.fill_pairs(batch["a_idx"], batch["a_val"], ids)
+        elif has_a:
             batch["a"] = s["a"][:b]
             table.fill_answers(batch["a"], ids)
         return batch

@@ -43,9 +43,23 @@ def _check_k(C, k):
         raise ValueError("k=%d outside [1, min(16, C=%d)]" % (k, C))
 
 
+def _dense(logits, target):
+    """A sparse answer target -- the pair (a_idx int32 [B,K], a_val float32 [B,K]) or a dict holding the two -- as the dense
+    [B,C] row it stands for (ops.densify); anything else as it is."""
+    if isinstance(target, dict):
+        target = (target["a_idx"], target["a_val"])
+    if isinstance(target, (tuple, list)):
+        from . import ops
+        a_idx, a_val = target
+        return ops.densify(a_idx, a_val, logits.size(1))
+    return target
+
+
 def topk_hits(logits, target, kmax):
-    """int32 [kmax]: hits[j] = rows whose target ranks <= j.  target: [B,C] soft targets, or (CPU tensors) integer classes [B]."""
+    """int32 [kmax]: hits[j] = rows whose target ranks <= j.  target: [B,C] soft targets, a sparse pair (a_idx, a_val) of them
+    (ops.densify), or (CPU tensors) integer classes [B]."""
     logits = logits.detach()
+    target = _dense(logits, target)
     _check_k(logits.size(1), int(kmax))
     if logits.is_cuda:
         from . import ops

@@ -1874,6 +1874,128 @@ def ce_mean_loss_and_grad_hits(logits, labels, kmax, scale=None, check=True):
     return _loss_and_grad("CE", logits, labels, 1.0 / max(logits.shape[0], 1) if scale is None else scale, kmax)
 
 
+# ---- sparse answer targets (csrc/loss_sparse.hip) --------------------------------------------------------------------
+MAX_PAIRS = 16        # pairs per row the sparse loss kernels take
+_SPARSE_NAMES = {"KLD": "kld_sum_loss_sparse", "BCE": "bce_mean_loss_sparse", "CE": "ce_mean_loss_sampled"}
+
+
+def check_sparse_target(name, a_idx, a_val, rows=None):
+    """The format of a sparse answer target, refused as ValueError: a_idx int32 [B,K] and a_val float32 [B,K] on one device,
+    1 <= K <= MAX_PAIRS (and B == rows when given)."""
+    for w, t, d in (("a_idx", a_idx, torch.int32), ("a_val", a_val, torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != d:
+            raise ValueError("%s: %s must be a %s tensor, got %s" % (name, w, d, t.dtype if isinstance(t, torch.Tensor) else type(t)))
+    if a_idx.dim() != 2 or a_idx.shape != a_val.shape or a_idx.device != a_val.device:
+        raise ValueError("%s: a_idx and a_val must both be [B,K] on one device, got %s and %s"
+                         % (name, tuple(a_idx.shape), tuple(a_val.shape)))
+    if not 1 <= a_idx.size(1) <= MAX_PAIRS:
+        raise ValueError("%s: K=%d pairs per row outside [1, %d]" % (name, a_idx.size(1), MAX_PAIRS))
+    if rows is not None and a_idx.size(0) != rows:
+        raise ValueError("%s: %d rows of pairs for %d rows of logits" % (name, a_idx.size(0), rows))
+
+
+def live_pairs(a_idx, C):
+    """bool [B,K]: entry j of a row counts iff 0 <= a_idx[j] < C and no later entry of the row has the same id."""
+    K = a_idx.size(1)
+    later = torch.triu(torch.ones(K, K, dtype=torch.bool, device=a_idx.device), diagonal=1)         # [j, j'] : j' > j
+    shadowed = ((a_idx[:, :, None] == a_idx[:, None, :]) & later).any(2)
+    return (a_idx >= 0) & (a_idx < C) & ~shadowed
+
+
+def densify(a_idx, a_val, C):
+    """The dense soft target [B,C] a sparse one stands for -- the definition of the format, in plain torch ops on any device:
+    ``a[:] = 0; for j in order: a[a_idx[j]] = a_val[j]`` per row (datasets.py:963-969; the last pair of a duplicated id wins),
+    entries with an id outside [0, C) (the -1 padding) ignored."""
+    C = int(C)
+    check_sparse_target("densify", a_idx, a_val)
+    live = live_pairs(a_idx, C)
+    a = torch.zeros(a_idx.size(0), C + 1, dtype=torch.float32, device=a_idx.device)
+    # every entry that does not count goes to a spare column with value 0: the live ids of a row are distinct, so the scatter
+    # writes no real column twice
+    a.scatter_(1, torch.where(live, a_idx, torch.full_like(a_idx, C)).to(torch.int64), torch.where(live, a_val, torch.zeros_like(a_val)))
+    return a[:, :C].contiguous()
+
+
+def sparse_loss_and_grad(kind, logits, a_idx, a_val, scale=None, kmax=None, seed=None, row_offset=0):
+    """The host side of the sparse loss entry points below: checks, buffers, one launch -> (loss, d_logits, hits or None) for
+    kind "KLD" / "BCE", (loss, d_logits, hits or None, labels int64 [B]) for "CE", whose label is drawn on the device from the
+    pairs.  scale: None = the mean over this batch (BCE 1 / (B * C), CE 1 / B; KLD is a sum and takes none).  seed (CE): an int
+    host seed, a (device int64 tensor, salt) pair, or None = next_dropout_seed() -- a device word plus salt inside a trainer
+    step, a fresh host seed otherwise.  row_offset: added to the row number in the draw's counter (rank * B_local)."""
+    name = _SPARSE_NAMES[kind]
+    if isinstance(logits, torch.Tensor) and logits.dtype != torch.float32:
+        raise ValueError("%s: logits must be torch.float32, got %s" % (name, logits.dtype))
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.size(0) == 0 or logits.size(1) == 0:
+        raise ValueError("%s: logits must be a non-empty [B,C] tensor" % name)
+    check_sparse_target(name, a_idx, a_val, logits.size(0))
+    lg = _prep("logits", logits.detach())
+    a_idx, a_val = _prep("a_idx", a_idx, (torch.int32,)), _prep("a_val", a_val, (torch.float32,))
+    B, C = lg.shape
+    K = a_idx.size(1)
+    args = []
+    if kind != "KLD":
+        scale = 1.0 / (B * (C if kind == "BCE" else 1)) if scale is None else float(scale)
+        if not 0.0 < scale < float("inf"):
+            raise ValueError("%s: scale=%r must be positive and finite" % (name, scale))
+        args = [scale]
+    labels = None
+    if kind == "CE":
+        sv, sp = _seed_args(next_dropout_seed() if seed is None else seed)
+        if not 0 <= int(row_offset) < 2 ** 63:
+            raise ValueError("%s: row_offset=%r must be a non-negative integer" % (name, row_offset))
+        labels = torch.empty(B, device=lg.device, dtype=torch.int64)
+        args += [sv, sp, int(row_offset)]
+    lib = _lib.lib()
+    hits, shape = None, (B, C, K)
+    if kmax is not None:
+        kmax, name = int(kmax), name + "_hits"
+        _check_k(name, C, kmax)
+        hits, shape = torch.empty(kmax, device=lg.device, dtype=torch.int32), (B, C, K, kmax)
+        args = [_p(hits), kmax] + args
+    nbytes = lib.vqa_sparse_loss_workspace_bytes(B, kmax or 0)
+    loss = torch.empty((), device=lg.device, dtype=torch.float32)
+    d_logits = torch.empty_like(lg)
+    ws = torch.empty(nbytes // 4, device=lg.device, dtype=torch.float32)
+    head = [_p(lg), _p(a_idx), _p(a_val)] + ([_p(labels)] if kind == "CE" else [])
+    _launch(name, shape, getattr(lib, "vqa_" + name), *head, _p(loss), _p(d_logits), *args, _p(ws), nbytes, B, C, K)
+    return (loss, d_logits, hits) if kind != "CE" else (loss, d_logits, hits, labels)
+
+
+def kld_sum_loss_and_grad_sparse(logits, a_idx, a_val):
+    """kld_sum_loss_and_grad on the sparse target (a_idx int32 [B,K], a_val float32 [B,K]; see densify): the sums over the
+    target run over the live pairs, no dense [B,C] target is built or read."""
+    return sparse_loss_and_grad("KLD", logits, a_idx, a_val)[:2]
+
+
+def kld_sum_loss_and_grad_sparse_hits(logits, a_idx, a_val, kmax):
+    """kld_sum_loss_and_grad_sparse (bitwise the same loss and d_logits) plus hits int32[kmax] as kld_sum_loss_and_grad_hits counts them."""
+    return sparse_loss_and_grad("KLD", logits, a_idx, a_val, kmax=kmax)
+
+
+def bce_mean_loss_and_grad_sparse(logits, a_idx, a_val, scale=None):
+    """bce_mean_loss_and_grad on the sparse target."""
+    return sparse_loss_and_grad("BCE", logits, a_idx, a_val, scale)[:2]
+
+
+def bce_mean_loss_and_grad_sparse_hits(logits, a_idx, a_val, kmax, scale=None):
+    """bce_mean_loss_and_grad_sparse (bitwise the same loss and d_logits) plus hits int32[kmax]."""
+    return sparse_loss_and_grad("BCE", logits, a_idx, a_val, scale, kmax)
+
+
+def ce_mean_loss_and_grad_sampled(logits, a_idx, a_val, scale=None, seed=None, row_offset=0):
+    """(loss, d_logits, labels): cf.samplingans' step on the device -- per row a label is drawn from the pairs with the
+    probabilities a_val / sum(a_val) (datasets.py:952-959 draws it on the host per item), then loss and gradient are
+    ce_mean_loss_and_grad's with those labels.  labels int64 [B]; -1 (loss 0, gradient 0) for a row without a positive pair."""
+    loss, d_logits, _, labels = sparse_loss_and_grad("CE", logits, a_idx, a_val, scale, None, seed, row_offset)
+    return loss, d_logits, labels
+
+
+def ce_mean_loss_and_grad_sampled_hits(logits, a_idx, a_val, kmax, scale=None, seed=None, row_offset=0):
+    """(loss, d_logits, hits, labels): ce_mean_loss_and_grad_sampled (bitwise the same loss, d_logits and labels) plus hits
+    int32[kmax] against the drawn labels; a row with label -1 is never a hit."""
+    return sparse_loss_and_grad("CE", logits, a_idx, a_val, scale, kmax, seed, row_offset)
+
+
 def predict_topk(logits, k, target=None, probs=True):
     """The k best columns of every row in order (int64 [B,k]; column 0 = argmax), the softmax over the whole row at those
     columns ([B,k], or None with probs=False) and, with a target [B,C], its top-j hits (int32 [k]; else None)."""

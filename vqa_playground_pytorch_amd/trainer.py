@@ -27,6 +27,34 @@ def kld_sum_loss(logits, target):
     return F.kl_div(F.log_softmax(logits, dim=1), target, reduction="sum")
 
 
+class SparseTarget:
+    """A step's answer target as the feed's (answer id, probability) pairs -- a_idx int32 [B,K], a_val float32 [B,K], the
+    format ops.densify defines -- with the few tensor methods the step's graph bookkeeping uses on a dense target: the pair
+    is a graph input like the dense ``a`` (compared by shape and address, cloned into a private buffer, copied into it)."""
+
+    __slots__ = ("a_idx", "a_val")
+
+    def __init__(self, a_idx, a_val):
+        from . import ops
+        ops.check_sparse_target("step", a_idx, a_val)
+        self.a_idx, self.a_val = a_idx, a_val
+
+    @property
+    def shape(self):
+        return ("sparse",) + tuple(self.a_idx.shape)
+
+    def data_ptr(self):
+        return (self.a_idx.data_ptr(), self.a_val.data_ptr())
+
+    def clone(self):
+        return SparseTarget(self.a_idx.clone(), self.a_val.clone())
+
+    def copy_(self, other, non_blocking=False):
+        self.a_idx.copy_(other.a_idx, non_blocking=non_blocking)
+        self.a_val.copy_(other.a_val, non_blocking=non_blocking)
+        return self
+
+
 _HIP_NODE_TYPES = {0: "kernel", 1: "memcpy", 2: "memset", 3: "host", 4: "graph", 5: "empty", 6: "wait_event",
                    7: "event_record"}
 
@@ -258,6 +286,7 @@ class DataParallelTrainer:
             raise ValueError("topk=%s: every k must lie in [1, 16] (and not exceed the number of answers)" % (topk,))
         self.kmax = max(self.topk) if self.topk else 0
         self._front_out = (None, None, 0)    # (hits, logits, local batch) of the last step's loss launch
+        self._labels = None                  # CE from a sparse target: the labels the last step's loss launch drew
         self.group = group
         self.clip = clip
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
@@ -426,7 +455,12 @@ class DataParallelTrainer:
         """One training step on this rank's shard; returns (local loss tensor, global grad norm tensor).
         Replayed steps return the graph's OWN output tensors: the same two tensors every step, overwritten by the next
         replay -- read them (``.item()`` / ``.clone()``) before the next step if you keep a history; eager steps return
-        fresh tensors."""
+        fresh tensors.
+        target: the dense soft answers [B,C] (KLD / BCE) or int64 labels [B] (CE) -- or the sparse pair of the feed,
+        ``{"a_idx": int32 [B,K], "a_val": float32 [B,K]}`` (a whole batch dict will do: the two keys are picked out of it), from
+        which KLD and BCE are computed directly and CE draws its label per row and step (``last_labels``)."""
+        if isinstance(target, dict):
+            target = SparseTarget(target["a_idx"], target["a_val"])
         if self.hip and self.want_graph:
             return self._graph_step(sample, target)
         return self.step_eager(sample, target)
@@ -444,8 +478,15 @@ class DataParallelTrainer:
         """The logits [B,C] of the last step on this rank (with topk; None otherwise), under the same lifetime rule."""
         return self._front_out[1]
 
+    @property
+    def last_labels(self):
+        """int64 [B]: the labels the last CE step drew from its sparse target on THIS rank (-1: a row without a positive pair;
+        None for every other step), under last_hits' lifetime rule: each input slot's graph owns its tensor."""
+        return self._labels
+
     def accuracy(self):
-        """(Acc@k for k in topk), in percent, of the last step over the GLOBAL batch.  Synchronises with the device (the
+        """(Acc@k for k in topk), in percent, of the last step over the GLOBAL batch (CE from a sparse target: against the
+        labels that step drew, as the reference's accuracy(output, a) sees its sampled a).  Synchronises with the device (the
         counts are read back), and with more than one rank it all-reduces the hit counts and the batch size -- a
         collective: every rank must call it.  step() itself never does either."""
         if not self.topk:
@@ -471,6 +512,18 @@ class DataParallelTrainer:
     def _loss_and_grad(self, logits, target):
         """(loss, dL/dlogits) of the fused loss kernel -- with topk, its variant that also counts the hits."""
         from . import ops
+        if isinstance(target, SparseTarget):
+            # the pairs as they are: KLD / BCE over the live pairs, CE with its label drawn on the device from the step's seed
+            # (ranks that share a seed draw independently: the counter starts at rank * B_local)
+            rank = dist.get_rank(self.group) if self.world > 1 else 0
+            out = ops.sparse_loss_and_grad(self.loss_kind, logits, target.a_idx, target.a_val,
+                                           None if self.loss_kind == "KLD" else self._loss_scale(logits),
+                                           self.kmax if self.topk else None, None, rank * logits.size(0))
+            self._labels = out[3] if self.loss_kind == "CE" else None
+            if out[2] is not None:
+                self._front_out = (out[2], logits.detach(), logits.size(0))
+            return out[0], out[1]
+        self._labels = None
         # CE: labels outside [0, C) are refused on the host -- except inside a capture, which reads nothing back (the
         # kernel clamps the index, so a replayed step stays in bounds whatever the labels are)
         if self.loss_kind == "CE" and not torch.cuda.is_current_stream_capturing():
@@ -499,6 +552,25 @@ class DataParallelTrainer:
         else:
             return kld_sum_loss(logits, target)
         return loss / self.world if self.world > 1 else loss
+
+    def _cpu_sparse_loss(self, logits, target):
+        """The CPU step on a sparse target -> (loss, the target the hits are counted against): KLD / BCE on the dense row it
+        stands for (ops.densify), CE on labels drawn with torch.multinomial from torch's generator (-1, which adds nothing to
+        loss or gradient, for a row without a positive pair)."""
+        from . import ops
+        C = logits.size(1)
+        if self.loss_kind != "CE":
+            dense = ops.densify(target.a_idx, target.a_val, C)
+            return self._cpu_loss(logits, dense), dense
+        w = torch.where(ops.live_pairs(target.a_idx, C), target.a_val, torch.zeros_like(target.a_val))
+        drawable = w.sum(1) > 0
+        pick = torch.multinomial(torch.where(drawable[:, None], w, torch.ones_like(w)), 1)[:, 0]
+        labels = torch.where(drawable, target.a_idx.gather(1, pick[:, None])[:, 0].to(torch.int64), torch.full_like(pick, -1))
+        self._labels = labels
+        if bool(drawable.all()):
+            return self._cpu_loss(logits, labels), labels
+        loss = F.cross_entropy(logits, labels, ignore_index=-1, reduction="sum") / (logits.size(0) * self.world)
+        return loss, labels
 
     def _optimizer_launch(self, lr=None):
         """The optimizer pass of the GPU tail on the clipped gradients: lr given -> a launch argument (eager steps), None ->
@@ -531,10 +603,19 @@ class DataParallelTrainer:
             self._optimizer_launch(lr)
             return loss, f.norm_and_coef[0]
         logits = self.model(sample)
-        loss = self._cpu_loss(logits, target)
+        self._labels = None
+        if isinstance(target, SparseTarget):
+            loss, target = self._cpu_sparse_loss(logits, target)
+        else:
+            loss = self._cpu_loss(logits, target)
         if self.topk:
             from . import metrics
-            self._front_out = (metrics.topk_hits(logits, target, self.kmax), logits.detach(), logits.size(0))
+            if self._labels is not None:       # a row without a label ranks C: never a hit
+                rank = metrics.target_rank(logits.detach(), target.clamp(min=0))
+                hits = metrics._hits_from_rank(torch.where(target < 0, logits.size(1), rank), self.kmax)
+            else:
+                hits = metrics.topk_hits(logits, target, self.kmax)
+            self._front_out = (hits, logits.detach(), logits.size(0))
         for gp in self.optimizer.param_groups:
             gp["lr"] = self._advance_lr()
         self.grads.zero()
@@ -663,7 +744,7 @@ class DataParallelTrainer:
             if target.data_ptr() != g["target"].data_ptr():
                 g["target"].copy_(target, non_blocking=True)
         self._set_step_scalars()
-        self._front_out = slot["out"]
+        self._front_out, self._labels = slot["out"], slot["labels"]
         self._run_phases(slot=slot)
         g["tail"].replay()
         return slot["loss"], f.norm_and_coef[0]
@@ -708,7 +789,7 @@ class DataParallelTrainer:
                          if isinstance(v, torch.Tensor) and k in self._model_keys(sample)}
         if not self.adopt_inputs:
             target = target.clone()
-        eager_out = self._front_out         # the step that ran just before the capture stays "the last step"
+        eager_out, eager_labels = self._front_out, self._labels     # the step that ran just before the capture stays "the last step"
         # torch's capture recipe: one forward+backward on a side stream first, so the parameters' AccumulateGrad
         # nodes belong to a capturable stream (nodes created on the default stream would run there and abort the
         # capture).  It only refills the gradient buffer; no parameter is updated.
@@ -733,8 +814,9 @@ class DataParallelTrainer:
             with torch.cuda.graph(graph, pool=pool, capture_error_mode=mode):
                 outs.append(self._phase(i, static_sample, target))
         captured_out, self._front_out = self._front_out, eager_out
+        captured_labels, self._labels = self._labels, eager_labels
         self.graph_nodes.update(audit_and_instantiate(graphs, "step"))
-        return dict(graphs, loss=outs[0], out=captured_out, sample=static_sample, target=target, mode=mode)
+        return dict(graphs, loss=outs[0], out=captured_out, labels=captured_labels, sample=static_sample, target=target, mode=mode)
 
     # ---- backward in two halves, the first all-reduce under the second (overlap=True) ---------------------------------
     def _front_a(self, sample, target, device_seed=True):
