@@ -208,10 +208,12 @@ using namespace vqa;
 
 extern "C" size_t vqa_column_sum_workspace_bytes(int M, int N) {
   if (M <= 0 || N <= 0 || M <= kColShortM) return 0;
-  // the slab count depends on the vector width chosen at launch; size for the largest (vec = 1 gives the fewest column
-  // blocks per row of workgroups, hence the most slabs -- bounded by the rows)
+  // the slab count depends on the vector width chosen at launch (the wider the vector, the fewer column blocks, the more
+  // slabs -- bounded by the rows); size for the largest over the widths column_vec can choose for this N: N % vec == 0.
+  // (An odd N only ever runs at vec = 1: sizing it for vec = 4 asked for a workspace where S == 1 needs none.)
   int worst = 1;
-  for (int vec = 1; vec <= 4; vec *= 2) worst = column_slabs(M, N, vec) > worst ? column_slabs(M, N, vec) : worst;
+  for (int vec = 1; vec <= 4; vec *= 2)
+    if (N % vec == 0) worst = column_slabs(M, N, vec) > worst ? column_slabs(M, N, vec) : worst;
   return worst > 1 ? (size_t)worst * N * sizeof(float) : 0;
 }
 

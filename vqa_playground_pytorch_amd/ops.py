@@ -2035,24 +2035,59 @@ def predict_candidates(logits, cand):
     return pred
 
 
+def _device_floats(name, what, t, like, least):
+    """`t` is a contiguous float32 tensor of at least `least` elements on `like`'s device, or ValueError: the optimizer kernels
+    read and write these small buffers by address alone."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < least \
+            or t.device != like.device:
+        raise ValueError("%s: %s must be a contiguous torch.float32 tensor of at least %d elements on %s"
+                         % (name, what, least, like.device))
+
+
 def grad_norm_clip_coef(g_flat, max_norm, out, workspace):
     """out[0] = ||g_flat||_2, out[1] = min(1, max_norm/(norm+1e-6)) -- clip_grad_norm_ semantics (train.py:82)."""
-    g_flat = _prep("g_flat", g_flat)
+    if isinstance(g_flat, torch.Tensor) and g_flat.dtype != torch.float32:
+        raise ValueError("grad_norm_clip_coef: g must be torch.float32, got %s" % g_flat.dtype)
+    if _prep("g_flat", g_flat) is not g_flat:
+        raise ValueError("grad_norm_clip_coef: g must be contiguous")
+    if g_flat.numel() == 0:
+        raise ValueError("grad_norm_clip_coef: g is empty")
+    _device_floats("grad_norm_clip_coef", "out", out, g_flat, 2)
+    need = _lib.lib().vqa_grad_norm_workspace_bytes()
+    if not isinstance(workspace, torch.Tensor) or not workspace.is_contiguous() or workspace.device != g_flat.device \
+            or workspace.numel() * workspace.element_size() < need:
+        raise ValueError("grad_norm_clip_coef: the workspace must be a contiguous tensor of at least %d bytes on %s"
+                         % (need, g_flat.device))
     _launch("grad_norm_clip_coef", (g_flat.numel(),), _lib.lib().vqa_grad_norm_clip_coef, _p(g_flat), g_flat.numel(),
             float(max_norm), _p(out), _p(workspace), workspace.numel() * workspace.element_size())
 
 
+def _flat_adam(name, p_flat, g_flat, m_flat, v_flat, norm_and_coef):
+    for what, t in (("p", p_flat), ("g", g_flat), ("m", m_flat), ("v", v_flat)):
+        if isinstance(t, torch.Tensor) and t.dtype != torch.float32:
+            raise ValueError("%s: %s must be torch.float32, got %s" % (name, what, t.dtype))
+        if _prep(what, t) is not t:
+            raise ValueError("%s: %s must be contiguous" % (name, what))
+        if t.numel() != p_flat.numel() or t.numel() == 0 or t.device != p_flat.device:
+            raise ValueError("%s: p, g, m and v must hold the same, non-zero number of elements on one device" % name)
+    if norm_and_coef is not None:
+        _device_floats(name, "norm_and_coef", norm_and_coef, p_flat, 2)
+
+
 def adam_step(p_flat, g_flat, m_flat, v_flat, norm_and_coef, lr, beta1, beta2, eps, step):
-    """One fused Adam update of the flat parameter buffer on gradients scaled by norm_and_coef[1] (train.py:86)."""
-    for name, t in (("p", p_flat), ("g", g_flat), ("m", m_flat), ("v", v_flat)):
-        if _prep(name, t) is not t:
-            raise ValueError("adam_step: %s must be contiguous" % name)
+    """One fused Adam update of the flat parameter buffer on gradients scaled by norm_and_coef[1] (None: unscaled)
+    (train.py:86)."""
+    _flat_adam("adam_step", p_flat, g_flat, m_flat, v_flat, norm_and_coef)
+    if int(step) < 1:
+        raise ValueError("adam_step: step counts from 1, got %r" % (step,))
     _launch("adam_step", (p_flat.numel(),), _lib.lib().vqa_adam_step, _p(p_flat), _p(g_flat), _p(m_flat), _p(v_flat),
             p_flat.numel(), _p(norm_and_coef), float(lr), float(beta1), float(beta2), float(eps), int(step))
 
 
 def adam_step_dyn(p_flat, g_flat, m_flat, v_flat, norm_and_coef, step_scalars, beta1, beta2, eps):
     """adam_step with {lr/(1-b1^t), 1/sqrt(1-b2^t)} read from the device tensor ``step_scalars`` (graph replays)."""
+    _flat_adam("adam_step_dyn", p_flat, g_flat, m_flat, v_flat, norm_and_coef)
+    _device_floats("adam_step_dyn", "step_scalars", step_scalars, p_flat, 2)
     _launch("adam_step_dyn", (p_flat.numel(),), _lib.lib().vqa_adam_step_dyn, _p(p_flat), _p(g_flat), _p(m_flat),
             _p(v_flat), p_flat.numel(), _p(norm_and_coef), _p(step_scalars), float(beta1), float(beta2), float(eps))
 
