@@ -1,0 +1,239 @@
+// Mixed-precision recurrent path of the BayesianGRU question encoder: the per-step products of ops.GruSequenceBf16 as ONE bf16
+// product each (v_mfma_f32_32x32x16_bf16: bf16 operands, fp32 accumulation) instead of the split engine's six partial products
+// (csrc/gru_gemm.hip), and the gate kernels of csrc/gru.hip with bf16 GEMM-operand histories.
+//
+// Arithmetic contract (bf(.) = round to nearest even to bf16; step t of putils.BayesianGRU.forward, putils/__init__.py:604-646,
+// 691-731):
+//   weights   Wb_g = bf(W_hg), g in {r, i, n}: a bf16 shadow packed once per forward pass from the fp32 masters, and its transpose
+//             once per backward pass (vqa_pack_bf16); the masters stay fp32
+//   forward   hm_t[g] = bf(h_{t-1} * m_g)            the product formed in fp32, rounded once (no masks: bf(h_{t-1}))
+//             a[g]    = hm_t[g] Wb_g^T               fp32 accumulation, fp32 result
+//             gates exactly as csrc/gru.hip: h, r, i, n, a_n stay fp32
+//   backward  dzr, dzi, dzn, dan in fp32 as csrc/gru.hip forms them; d_gi is fp32 and unrounded
+//             gzb_t[g] = bf(gz_t[g])                 the GEMM operand
+//             dhm      = gzb_t[g] Wb_g               fp32 accumulation, fp32 result
+//             dW_g     = sum_t gzb_t[g]^T hm_t[g]    over all T*B rows: vqa_gemm_bf16_tn, fp32, fixed-order slabs, no atomics
+//   The roundings are straight-through for the gradients.  Everything is bitwise reproducible from run to run.
+//
+// The GEMM.  G same-shaped products per launch, c_g[m][n] = sum_k a_g[m][k] * w_g[n][k], on gemm_bf16_mfma.hpp's NT tile loop
+// (two-stage LDS ring, global loads two stages ahead).  The contraction advances 64 at a time, so the caller pads operand ROWS
+// to a multiple of 64 elements with zeros (2400 -> 2432) and the kernel reads the pads; rows past M (or N) are read from the
+// clamped last row and reach only accumulator rows (columns) that are never stored -- an MFMA row depends on its own A row
+// alone, so any M >= 1 runs and a non-finite row stays in its row.
+// Tile and wave layout: 128 x 128 per workgroup, four waves 2 x 2, each wave 2 x 2 accumulators of 32 x 32.  Per 16-deep MFMA
+// step a wave then reads 2 + 2 ds_read_b128 fragments for 4 MFMAs = one read per 32-cycle MFMA slot, half of the two reads per
+// slot the LDS delivers for free (a third per slot would make the LDS array, not the matrix pipe, set the pace); a 64 x 64 tile
+// (one accumulator per wave) sits exactly at two.  At the training shape (M = 512, N = 2400, G = 3) 128 x 128 gives
+// 4 x 19 x 3 = 228 workgroups: one round on the 256 CUs at 89 % fill, where 128 x 64 or 64 x 128 need two rounds of half-sized
+// tiles (456 workgroups) at a worse read-to-MFMA ratio (1.5 per slot).  M <= 64 takes 64 x 128 so that a short batch does not
+// pay for 64 clamped rows.  Tiles are numbered row-tile-fastest inside a problem and handed out in contiguous ranges per XCD:
+// the (at most 8) row tiles of one column tile are neighbours and share that 128-row slice of the weights in their XCD's L2.
+#include "common.hpp"
+#include "gemm_bf16_mfma.hpp"
+
+namespace vqa {
+
+struct GruBfArgs {
+  const bf16* a;
+  long a_gs;
+  int lda;
+  const bf16* w;
+  long w_gs;
+  int ldw;
+  float* c;
+  long c_gs;
+  int ldc;
+  int M, N, Kp;          // Kp: the contraction rounded up to a multiple of 64 (the operand rows' zero pads)
+  int tiles_m, tiles_n;
+};
+
+template <int BM, int BN>
+__global__ __launch_bounds__(kBfThreads) void gru_gemm_bf16_kernel(GruBfArgs q) {
+  using T = BfTile<BM, BN>;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tiles = q.tiles_m * q.tiles_n;
+  const int lin = xcd_remap(blockIdx.x, gridDim.x);
+  const int prob = __builtin_amdgcn_readfirstlane(lin / tiles), tile = lin - prob * tiles;
+  const int m0 = (tile % q.tiles_m) * BM, n0 = (tile / q.tiles_m) * BN;
+  const bf16* A = q.a + (size_t)prob * q.a_gs;
+  const bf16* W = q.w + (size_t)prob * q.w_gs;
+  float* C = q.c + (size_t)prob * q.c_gs;
+  f32x16 acc[T::TM][T::TN];
+  bf_zero_acc(acc);
+  gemm_bf16_nt_tile<BM, BN>(A, q.lda, q.M, W, q.ldw, q.N, m0, n0, q.Kp, smem, acc);
+  const BfAccCoord<BM, BN> cc(m0, n0);
+  const unsigned lo = cc.loff(q.ldc);
+#pragma unroll
+  for (int tn = 0; tn < T::TN; ++tn) {
+    if (cc.col(tn) >= q.N) continue;
+#pragma unroll
+    for (int tm = 0; tm < T::TM; ++tm)
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (cc.row(tm, i) < q.M) (C + cc.uoff(tm, tn, i, q.ldc))[lo] = acc[tm][tn][i];
+  }
+}
+
+// ---- gate kernels: csrc/gru.hip's, with the GEMM-operand histories in bf16 ------------------------------------------------
+__device__ __forceinline__ float sigmoidf(float z) { return 1.f / (1.f + expf(-z)); }
+__device__ __forceinline__ float gru_af(float z, int af) { return af == 1 ? fmaxf(z, 0.f) : tanhf(z); }
+__device__ __forceinline__ float gru_af_grad(float n, int af) { return af == 1 ? (n > 0.f ? 1.f : 0.f) : 1.f - n * n; }
+
+#define VQA_GRU_FOR4(EXPR)                 \
+  {                                        \
+    { constexpr int c = 0; EXPR; }         \
+    { constexpr int c = 1; EXPR; }         \
+    { constexpr int c = 2; EXPR; }         \
+    { constexpr int c = 3; EXPR; }         \
+  }
+__device__ __forceinline__ float& f4(float4& v, int c) { return reinterpret_cast<float*>(&v)[c]; }
+__device__ __forceinline__ float f4(const float4& v, int c) { return reinterpret_cast<const float*>(&v)[c]; }
+
+// as gru_gates_fwd_kernel; hm_next: base of slot t+1 of the bf16 [3,T,B,ld] history (group stride hist_gs, row stride ld) or null
+__global__ __launch_bounds__(256) void gru_gates_fwd_bf16_kernel(const float* __restrict__ gi, const float* __restrict__ a,
+                                                                 const float* __restrict__ h_prev,
+                                                                 const float* __restrict__ masks, float* __restrict__ h_new,
+                                                                 bf16* __restrict__ hm_next, size_t hist_gs, int ld,
+                                                                 float* __restrict__ r_s, float* __restrict__ i_s,
+                                                                 float* __restrict__ n_s, float* __restrict__ an_s, int B, int T,
+                                                                 int H, int t, int af) {
+  const size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  const size_t BH = (size_t)B * H;
+  if (e >= BH) return;
+  const size_t b = e / H, h = e % H;
+  const size_t gio = (b * T + t) * H + h, gig = (size_t)B * T * H;
+  const float4 gr = ld4(gi + gio), gz = ld4(gi + gig + gio), gn = ld4(gi + 2 * gig + gio);
+  const float4 ar = ld4(a + e), ai = ld4(a + BH + e), an = ld4(a + 2 * BH + e);
+  const float4 hp = ld4(h_prev + e);
+  float4 r, i, n, hn;
+  VQA_GRU_FOR4(f4(r, c) = sigmoidf(f4(gr, c) + f4(ar, c)); f4(i, c) = sigmoidf(f4(gz, c) + f4(ai, c));
+               f4(n, c) = gru_af(f4(gn, c) + f4(r, c) * f4(an, c), af);
+               f4(hn, c) = (1.f - f4(i, c)) * f4(n, c) + f4(i, c) * f4(hp, c));
+  st4(h_new + e, hn);
+  st4(r_s + e, r);
+  st4(i_s + e, i);
+  st4(n_s + e, n);
+  st4(an_s + e, an);
+  if (hm_next != nullptr) {
+    const size_t ho = b * (size_t)ld + h;
+#pragma unroll
+    for (int g = 0; g < 3; ++g) st4(hm_next + g * hist_gs + ho, masks != nullptr ? mul4(hn, ld4(masks + g * BH + e)) : hn);
+  }
+}
+
+// as gru_gates_bwd_kernel; gz: slot t of the bf16 [3,T,B,ld] history (bf(dzr), bf(dzi), bf(dan)); d_gi stays fp32, unrounded
+__global__ __launch_bounds__(256) void gru_gates_bwd_bf16_kernel(const float* __restrict__ d_out_t,
+                                                                 const float* __restrict__ carry_in,
+                                                                 const float* __restrict__ dhm, const float* __restrict__ masks,
+                                                                 const float* __restrict__ r_s, const float* __restrict__ i_s,
+                                                                 const float* __restrict__ n_s, const float* __restrict__ an_s,
+                                                                 const float* __restrict__ h_prev, bf16* __restrict__ gz,
+                                                                 size_t hist_gs, int ld, float* __restrict__ d_gi,
+                                                                 float* __restrict__ carry_out, int B, int T, int H, int t,
+                                                                 int af) {
+  const size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  const size_t BH = (size_t)B * H;
+  if (e >= BH) return;
+  const size_t b = e / H, h = e % H;
+  float4 dh = d_out_t != nullptr ? ld4(d_out_t + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+  if (carry_in != nullptr) dh = add4(dh, ld4(carry_in + e));
+  if (dhm != nullptr) {
+#pragma unroll
+    for (int g = 0; g < 3; ++g) {
+      const float4 d = ld4(dhm + g * BH + e);
+      dh = add4(dh, masks != nullptr ? mul4(d, ld4(masks + g * BH + e)) : d);
+    }
+  }
+  const float4 r = ld4(r_s + e), i = ld4(i_s + e), n = ld4(n_s + e), an = ld4(an_s + e), hp = ld4(h_prev + e);
+  float4 dzr, dzi, dzn, dan, co;
+  VQA_GRU_FOR4(const float d = f4(dh, c); const float dn = d * (1.f - f4(i, c)) * gru_af_grad(f4(n, c), af);
+               f4(dzn, c) = dn; f4(dan, c) = dn * f4(r, c);
+               f4(dzr, c) = dn * f4(an, c) * f4(r, c) * (1.f - f4(r, c));
+               f4(dzi, c) = d * (f4(hp, c) - f4(n, c)) * f4(i, c) * (1.f - f4(i, c)); f4(co, c) = d * f4(i, c));
+  const size_t ho = b * (size_t)ld + h;
+  st4(gz + ho, dzr);
+  st4(gz + hist_gs + ho, dzi);
+  st4(gz + 2 * hist_gs + ho, dan);
+  const size_t gio = (b * T + t) * H + h, gig = (size_t)B * T * H;
+  st4(d_gi + gio, dzr);
+  st4(d_gi + gig + gio, dzi);
+  st4(d_gi + 2 * gig + gio, dzn);
+  st4(carry_out + e, co);
+}
+
+static int gru_bf16_check(const char* who, const void* hist, size_t hist_gs, int ld, int B, int T, int H, int t, int af) {
+  VQA_REQUIRE(B > 0 && T > 0 && H > 0 && t >= 0 && t < T, VQA_E_BADARG, "%s: bad sizes B=%d T=%d H=%d t=%d", who, B, T, H, t);
+  VQA_REQUIRE(H % 8 == 0, VQA_E_UNSUPPORTED, "%s: needs H %% 8 == 0 (H=%d)", who, H);
+  VQA_REQUIRE(af == 1 || af == 3, VQA_E_BADARG, "%s: af must be 1 (relu) or 3 (tanh), got %d", who, af);
+  VQA_REQUIRE(hist == nullptr || ld >= H, VQA_E_BADARG, "%s: history row stride %d < H=%d", who, ld, H);
+  VQA_REQUIRE(hist == nullptr || (ld % 8 == 0 && hist_gs % 8 == 0 && aligned(hist, 16)), VQA_E_UNSUPPORTED,
+              "%s: the bf16 history needs ld %% 8 == 0, a group stride %% 8 == 0 and a 16-byte aligned slot", who);
+  return VQA_OK;
+}
+
+template <int BM, int BN>
+static int launch_gru_gemm_bf16(GruBfArgs q, int G, hipStream_t s) {
+  q.tiles_m = (q.M + BM - 1) / BM;
+  q.tiles_n = (q.N + BN - 1) / BN;
+  const size_t lds = BfTile<BM, BN>::kSmemBytes;
+  VQA_ENSURE_LDS((gru_gemm_bf16_kernel<BM, BN>), lds);
+  VQA_LAUNCH((gru_gemm_bf16_kernel<BM, BN>), dim3(q.tiles_m * q.tiles_n * G), dim3(kBfThreads), lds, s, q);
+  return check_launch("gru_gemm_bf16");
+}
+
+static int padded64(int K) { return (K + 63) / 64 * 64; }
+
+}  // namespace vqa
+
+using namespace vqa;
+
+extern "C" int vqa_gru_gemm_bf16_supported(int M, int N, int K, int lda, int ldw, int ldc) {
+  if (M < 1 || N < 8 || K < 8 || N % 8 != 0 || K % 8 != 0) return 0;
+  const int Kp = padded64(K);
+  return (lda % 8 == 0 && ldw % 8 == 0 && lda >= Kp && ldw >= Kp && ldc >= N && (size_t)M * lda < (1ull << 31) &&
+          (size_t)N * ldw < (1ull << 31) && (size_t)M * ldc < (1ull << 31)) ? 1 : 0;
+}
+
+extern "C" int vqa_gru_gemm_bf16(const vqa_bf16_t* a, long a_gs, int lda, const vqa_bf16_t* w, long w_gs, int ldw, float* c,
+                                 long c_gs, int ldc, int G, int M, int N, int K, vqa_stream_t stream) {
+  VQA_REQUIRE(a && w && c, VQA_E_BADARG, "gru_gemm_bf16: null pointer");
+  VQA_REQUIRE(G >= 1 && G <= 4096 && M >= 1 && N >= 1 && K >= 1 && a_gs >= 0 && w_gs >= 0 && c_gs >= 0, VQA_E_BADARG,
+              "gru_gemm_bf16: bad sizes G=%d M=%d N=%d K=%d", G, M, N, K);
+  VQA_REQUIRE(vqa_gru_gemm_bf16_supported(M, N, K, lda, ldw, ldc) == 1, VQA_E_UNSUPPORTED,
+              "gru_gemm_bf16: shape outside the kernel (M=%d N=%d K=%d lda=%d ldw=%d ldc=%d): N %% 8 == 0, K %% 8 == 0, operand rows "
+              "padded to a multiple of 64 elements (lda, ldw >= K rounded up to 64, %% 8 == 0), ldc >= N",
+              M, N, K, lda, ldw, ldc);
+  VQA_REQUIRE(aligned(a, 16) && aligned(w, 16) && aligned(c, 4) && a_gs % 8 == 0 && w_gs % 8 == 0, VQA_E_UNSUPPORTED,
+              "gru_gemm_bf16: a, w (and their problem strides) must be 16-byte aligned");
+  const GruBfArgs q{reinterpret_cast<const bf16*>(a), a_gs, lda, reinterpret_cast<const bf16*>(w), w_gs, ldw, c, c_gs, ldc,
+                    M, N, padded64(K), 0, 0};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (M <= 64) return launch_gru_gemm_bf16<64, 128>(q, G, s);
+  return launch_gru_gemm_bf16<128, 128>(q, G, s);
+}
+
+extern "C" int vqa_gru_gates_fwd_bf16(const float* gi, const float* a, const float* h_prev, const float* masks, float* h_new,
+                                      vqa_bf16_t* hm_next, size_t hist_group_stride, int ld, float* r_s, float* i_s, float* n_s,
+                                      float* an_s, int B, int T, int H, int t, int af, vqa_stream_t stream) {
+  VQA_REQUIRE(gi && a && h_prev && h_new && r_s && i_s && n_s && an_s, VQA_E_BADARG, "gru_gates_fwd_bf16: null pointer");
+  int rc = gru_bf16_check("gru_gates_fwd_bf16", hm_next, hist_group_stride, ld, B, T, H, t, af);
+  if (rc != VQA_OK) return rc;
+  const size_t n4 = (size_t)B * H / 4;
+  VQA_LAUNCH(gru_gates_fwd_bf16_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), gi,
+             a, h_prev, masks, h_new, reinterpret_cast<bf16*>(hm_next), hist_group_stride, ld, r_s, i_s, n_s, an_s, B, T, H, t, af);
+  return check_launch("gru_gates_fwd_bf16");
+}
+
+extern "C" int vqa_gru_gates_bwd_bf16(const float* d_out_t, const float* carry_in, const float* dhm, const float* masks,
+                                      const float* r_s, const float* i_s, const float* n_s, const float* an_s,
+                                      const float* h_prev, vqa_bf16_t* gz, size_t hist_group_stride, int ld, float* d_gi,
+                                      float* carry_out, int B, int T, int H, int t, int af, vqa_stream_t stream) {
+  VQA_REQUIRE(r_s && i_s && n_s && an_s && h_prev && gz && d_gi && carry_out, VQA_E_BADARG, "gru_gates_bwd_bf16: null pointer");
+  int rc = gru_bf16_check("gru_gates_bwd_bf16", gz, hist_group_stride, ld, B, T, H, t, af);
+  if (rc != VQA_OK) return rc;
+  const size_t n4 = (size_t)B * H / 4;
+  VQA_LAUNCH(gru_gates_bwd_bf16_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+             d_out_t, carry_in, dhm, masks, r_s, i_s, n_s, an_s, h_prev, reinterpret_cast<bf16*>(gz), hist_group_stride, ld, d_gi,
+             carry_out, B, T, H, t, af);
+  return check_launch("gru_gates_bwd_bf16");
+}

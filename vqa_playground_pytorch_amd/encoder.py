@@ -9,6 +9,8 @@ initialised.  Pure torch ops (library GEMMs) -- upstream of the path north_star 
 flow: the three input-side projections of all T steps are three [B*T,620]x[620,2400] GEMMs instead of 3*T small ones,
 and the last valid state is gathered instead of masked-and-summed.
 """
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -18,6 +20,24 @@ from . import ops
 
 def _af(name):
     return {"tanh": torch.tanh, "relu": F.relu, "sigmoid": torch.sigmoid}[name]
+
+
+class _RecurrentProductBf16(torch.autograd.Function):
+    """a = bf(hm) bf(W)^T with the backward of the mixed-precision contract (csrc/gru_bf16.hip) in torch ops: the incoming gradient
+    is rounded to bf16 for the two products it feeds, d_hm = bf(g) bf(W) and d_W = bf(g)^T bf(hm); the roundings themselves are
+    straight-through.  Operands keep their dtype (the bf16 VALUES in fp32 / fp64 storage), so the products accumulate in it."""
+
+    @staticmethod
+    def forward(ctx, hm, w):
+        hb, wb = hm.to(torch.bfloat16).to(hm.dtype), w.to(torch.bfloat16).to(w.dtype)
+        ctx.save_for_backward(hb, wb)
+        return hb @ wb.t()
+
+    @staticmethod
+    def backward(ctx, g):
+        hb, wb = ctx.saved_tensors
+        gb = g.to(torch.bfloat16).to(g.dtype)
+        return gb @ wb, gb.t() @ hb
 
 
 class BayesianGRUCell(nn.Module):
@@ -38,8 +58,12 @@ class BayesianGRU(nn.Module):
     """putils/__init__.py:672-746.  The six dropout masks are drawn once per sequence and shared by all time steps
     (SequentialDropout); ``forward(x [B,T,in], lengths [B]) -> [B,hidden]`` = the state at step lengths-1."""
 
-    def __init__(self, input_size, hidden_size, bias_ih=True, bias_hh=False, dropout=0.25, return_last=True, af="tanh"):
+    def __init__(self, input_size, hidden_size, bias_ih=True, bias_hh=False, dropout=0.25, return_last=True, af="tanh",
+                 compute_dtype=None):
         super().__init__()
+        # torch.bfloat16: the recurrent products in mixed precision (bf16 operands, fp32 accumulation; csrc/gru_bf16.hip states
+        # the contract, INTEGRATION.md section 2).  Parameters, state and the input side stay fp32 either way.
+        self.compute_dtype = ops.parse_compute_dtype(compute_dtype)
         self.input_size, self.hidden_size = input_size, hidden_size
         self.dropout, self.return_last, self.af = dropout, return_last, af
         self.gru_cell = BayesianGRUCell(input_size, hidden_size, bias_ih, bias_hh, dropout=dropout, af=af)
@@ -74,7 +98,7 @@ class BayesianGRU(nn.Module):
         w_in = ops.stack_params([m.weight for m in inp])
         b_in = ops.stack_params([m.bias for m in inp]) if inp[0].bias is not None else None
         gi = ops.batched_linear(xg, w_in, b_in, group_first=True).view(3, B, T, self.hidden_size)
-        out = ops.gru_sequence(gi, ops.stack_params([m.weight for m in hid]), mh, self.af)      # [T,B,H]
+        out = ops.gru_sequence(gi, ops.stack_params([m.weight for m in hid]), mh, self.af, self.compute_dtype)      # [T,B,H]
         if not self.return_last:
             return out.transpose(0, 1)
         self.all_hiddens = out.detach().transpose(0, 1)
@@ -84,8 +108,16 @@ class BayesianGRU(nn.Module):
     def forward(self, x, lengths=None):
         c, af = self.gru_cell, _af(self.af)
         B, T, _ = x.shape
-        if x.is_cuda and self.af in ("relu", "tanh") and c.weight_hr.bias is None and self.hidden_size % 4 == 0:
+        bf16 = self.compute_dtype == torch.bfloat16
+        # (the mixed-precision mode never falls back to fp32 products: a width its kernels do not take raises in ops.gru_sequence)
+        if x.is_cuda and self.af in ("relu", "tanh") and c.weight_hr.bias is None and (bf16 or self.hidden_size % 4 == 0):
             return self._forward_hip(x, lengths)
+
+        def recurrent(lin, hm):        # the same contract in torch ops: CPU tests and gloo runs see the same function
+            if not bf16:
+                return lin(hm)
+            a = _RecurrentProductBf16.apply(hm, lin.weight)
+            return a if lin.bias is None else a + lin.bias
         mx = [self._mask(x[:, :1, :]) for _ in range(3)]                       # [B,1,in], shared over time
         h = x.new_zeros(B, self.hidden_size)
         mh = [self._mask(h) for _ in range(3)]                                 # [B,hidden]
@@ -94,9 +126,9 @@ class BayesianGRU(nn.Module):
         outs = []
         for t in range(T):
             hr, hi, hn = (h if m is None else h * m for m in mh)
-            r = torch.sigmoid(gi[0][:, t] + c.weight_hr(hr))
-            i = torch.sigmoid(gi[1][:, t] + c.weight_hi(hi))
-            n = af(gi[2][:, t] + r * c.weight_hn(hn))
+            r = torch.sigmoid(gi[0][:, t] + recurrent(c.weight_hr, hr))
+            i = torch.sigmoid(gi[1][:, t] + recurrent(c.weight_hi, hi))
+            n = af(gi[2][:, t] + r * recurrent(c.weight_hn, hn))
             h = (1 - i) * n + i * h
             outs.append(h)
         output = torch.stack(outs, dim=1)                                      # [B,T,hidden]
@@ -107,16 +139,30 @@ class BayesianGRU(nn.Module):
         return output[torch.arange(B, device=x.device), idx]
 
 
+def encoder_dtype_from(encoder_dtype):
+    """The compute dtype of the encoder a model builds: the caller's ``encoder_dtype`` (validated), or, when that is None, the
+    environment variable VQA_ENCODER_DTYPE (``f32``, the default, or ``bf16``), read here -- where the encoder is built."""
+    if encoder_dtype is not None:
+        return ops.parse_compute_dtype(encoder_dtype, "encoder_dtype")
+    env = os.environ.get("VQA_ENCODER_DTYPE", "f32")
+    if env not in ("f32", "bf16"):
+        raise ValueError("VQA_ENCODER_DTYPE must be f32 or bf16, got %r" % (env,))
+    return torch.bfloat16 if env == "bf16" else torch.float32
+
+
 class SkipThoughts(nn.Module):
     """putils/__init__.py:878-985: ``forward(q_idxes int64 [B,T], 0 = PAD) -> [B,2400]``."""
 
-    def __init__(self, vocab_list, data_dir=None, gru="BayesianGRU", return_last=True, af="tanh", pretrained=None):
+    def __init__(self, vocab_list, data_dir=None, gru="BayesianGRU", return_last=True, af="tanh", pretrained=None,
+                 compute_dtype=None):
         super().__init__()
         if gru != "BayesianGRU":
             raise ValueError("only the BayesianGRU encoder of config/CoR2.py:166 / config/ODA.py:183 is provided")
         self.vocab_list, self.data_dir, self.af = vocab_list, data_dir, af
         self.embedding = nn.Embedding(num_embeddings=len(vocab_list), embedding_dim=620, padding_idx=0)
-        self.gru = BayesianGRU(input_size=620, hidden_size=2400, dropout=0.25, return_last=return_last, af=af)
+        self.gru = BayesianGRU(input_size=620, hidden_size=2400, dropout=0.25, return_last=return_last, af=af,
+                               compute_dtype=compute_dtype)
+        self.compute_dtype = self.gru.compute_dtype
         if pretrained is not None:
             self.load_pretrained(pretrained)
 

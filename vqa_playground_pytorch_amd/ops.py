@@ -1714,9 +1714,107 @@ class GruSequence(torch.autograd.Function):
         return d_gi, d_w, None, None
 
 
-def gru_sequence(gi, w, masks, af):
+def gru_gemm_bf16(a, a_off, a_gs, lda, w, w_gs, ldw, c, G, M, N, K):
+    """c[g] [M,N] fp32 (contiguous [G,M,N]) = a_g [M,K] w_g[N,K]^T, one bf16 product each with fp32 accumulation
+    (csrc/gru_bf16.hip: vqa_gru_gemm_bf16).  a, w: bf16 tensors holding the operands, a_g starting `a_off + g * a_gs` elements in,
+    rows of stride lda / ldw whose pads up to a multiple of 64 elements are zero."""
+    _launch("gru_gemm_bf16", (G, M, N, K), _lib.lib().vqa_gru_gemm_bf16, ctypes.c_void_p(a.data_ptr() + 2 * int(a_off)), int(a_gs),
+            int(lda), _p(w), int(w_gs), int(ldw), _p(c), M * N, N, G, M, N, K)
+    return c
+
+
+class GruSequenceBf16(torch.autograd.Function):
+    """GruSequence with the recurrent products in mixed precision (csrc/gru_bf16.hip states the contract): bf16 shadows of the
+    three recurrent weights (packed once per forward pass, transposed once per backward pass; the masters stay fp32), bf16
+    histories of the GEMM operands hm_t = bf(h_{t-1} * m_g) and gzb_t = bf(gz_t) with rows padded to a multiple of 64 (zero pads,
+    never written), fp32 accumulation, fp32 state / gates / saved tensors / d_gi.  Per step one vqa_gru_gemm_bf16 and one
+    vqa_gru_gates_*_bf16 launch each way; the recurrent weight gradient is three vqa_gemm_bf16_tn launches (fixed-order slabs)
+    over the two histories at the end.  Same loop structure as GruSequence; any B >= 1, H % 8 == 0."""
+
+    @staticmethod
+    def forward(ctx, gi, w, masks, af):
+        gi, w = _prep("gi", gi), _prep("w", w)
+        masks = _prep("masks", masks) if masks is not None else None
+        G, B, T, H = gi.shape
+        if G != 3 or w.shape != (3, H, H) or (masks is not None and masks.shape != (3, B, H)):
+            raise ValueError("gru_sequence: gi [3,B,T,H], w [3,H,H], masks [3,B,H] expected")
+        if H % 8:
+            raise ValueError("gru_sequence: compute_dtype=bfloat16 needs a hidden size that is a multiple of 8, got H = %d" % H)
+        code = {"relu": 1, "tanh": 3}[af]
+        dev = gi.device
+        L_ = _lib.lib()
+        Hp = pad_to(H)
+        out = torch.empty(T, B, H, device=dev, dtype=torch.float32)
+        hist = torch.zeros(3, T, B, Hp, device=dev, dtype=torch.bfloat16)      # hm_t = bf(h_{t-1} * m_g); hm_0 = 0
+        saved = torch.empty(4, T, B, H, device=dev, dtype=torch.float32)       # r, i, n, a_n
+        h0 = torch.zeros(B, H, device=dev, dtype=torch.float32)
+        a = torch.empty(3, B, H, device=dev, dtype=torch.float32)
+        gs = T * B * Hp
+        wb = pack_bf16(w, torch.zeros(3, H, Hp, device=dev, dtype=torch.bfloat16), H * Hp, Hp, 1, zero_fill=False)
+        for t in range(T):
+            if t == 0:
+                a.zero_()                                                        # hm_0 = 0: no product to form
+            else:
+                gru_gemm_bf16(hist, t * B * Hp, gs, Hp, wb, H * Hp, Hp, a, 3, B, H, H)                      # a[g] = hm_t[g] Wb_g^T
+            nxt = ctypes.c_void_p(hist.data_ptr() + 2 * (t + 1) * B * Hp) if t + 1 < T else None
+            _launch("gru_gates_fwd_bf16", (B, T, H), L_.vqa_gru_gates_fwd_bf16, _p(gi), _p(a), _p(out[t - 1] if t else h0), _p(masks),
+                    _p(out[t]), nxt, gs, Hp, _p(saved[0, t]), _p(saved[1, t]), _p(saved[2, t]), _p(saved[3, t]), B, T, H, t, code)
+        ctx.save_for_backward(w, masks, out, hist, saved, h0)
+        ctx.cfg = (B, T, H, Hp, code)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        w, masks, out, hist, saved, h0 = ctx.saved_tensors
+        B, T, H, Hp, code = ctx.cfg
+        d_out = _prep("grad_out", d_out)
+        dev = d_out.device
+        L_ = _lib.lib()
+        gz = torch.zeros(3, T, B, Hp, device=dev, dtype=torch.bfloat16)        # gzb_t = bf(gz_t)
+        d_gi = torch.empty(3, B, T, H, device=dev, dtype=torch.float32)
+        carry = [torch.empty(B, H, device=dev, dtype=torch.float32) for _ in range(2)]
+        gs = T * B * Hp
+        buf = torch.empty(3, B, H, device=dev, dtype=torch.float32)
+        wbt = pack_bf16(w, torch.zeros(3, H, Hp, device=dev, dtype=torch.bfloat16), H * Hp, 1, Hp, zero_fill=False)   # Wb_g^T
+        dhm = None
+        for t in range(T - 1, -1, -1):
+            _launch("gru_gates_bwd_bf16", (B, T, H), L_.vqa_gru_gates_bwd_bf16, _p(d_out[t]),
+                    _p(carry[(t + 1) & 1]) if t + 1 < T else None, _p(dhm), _p(masks), _p(saved[0, t]), _p(saved[1, t]),
+                    _p(saved[2, t]), _p(saved[3, t]), _p(out[t - 1] if t else h0), ctypes.c_void_p(gz.data_ptr() + 2 * t * B * Hp), gs,
+                    Hp, _p(d_gi), _p(carry[t & 1]), B, T, H, t, code)
+            if t > 0:                                                           # gradient at hm_t: dhm[g] = gzb_t[g] Wb_g   [3,B,H]
+                dhm = gru_gemm_bf16(gz, t * B * Hp, gs, Hp, wbt, H * Hp, Hp, buf, 3, B, H, H)
+        d_w = None
+        if ctx.needs_input_grad[1]:
+            # d_w[g] = gzb[g]^T hm[g] over all T*B rows, written straight into the gradient's slot
+            d_w = _grad_like(w)
+            ws_bytes = L_.vqa_gemm_bf16_tn_workspace_bytes(T * B, H, H)
+            ws = torch.empty((ws_bytes + 3) // 4, device=dev, dtype=torch.float32)
+            for g in range(3):
+                _launch("gemm_bf16_tn", (T * B, H, H), L_.vqa_gemm_bf16_tn, ctypes.c_void_p(gz.data_ptr() + 2 * g * gs), Hp,
+                        ctypes.c_void_p(hist.data_ptr() + 2 * g * gs), Hp, _p(d_w[g]), _p(ws), ws_bytes, T * B, H, H)
+        return d_gi, d_w, None, None
+
+
+def parse_compute_dtype(value, name="compute_dtype"):
+    """None / torch.float32 / torch.bfloat16 / 'bf16' / 'bfloat16' -> torch.float32 or torch.bfloat16 (the accepted values and the
+    error text of cor2.Model's compute_dtype)."""
+    if value is None:
+        return torch.float32
+    if isinstance(value, str) and value in ("bf16", "bfloat16"):
+        return torch.bfloat16
+    if isinstance(value, torch.dtype) and value in (torch.float32, torch.bfloat16):
+        return value
+    raise ValueError("%s must be None, torch.float32 or torch.bfloat16, got %r" % (name, value))
+
+
+def gru_sequence(gi, w, masks, af, compute_dtype=None):
+    """compute_dtype None / torch.float32: GruSequence (fp32 products on the split engine); torch.bfloat16 / 'bf16' / 'bfloat16':
+    GruSequenceBf16 (one bf16 product per recurrent GEMM, fp32 accumulation)."""
     if af not in ("relu", "tanh"):
         raise ValueError("gru_sequence: af must be 'relu' or 'tanh', got %r" % (af,))
+    if parse_compute_dtype(compute_dtype) == torch.bfloat16:
+        return GruSequenceBf16.apply(gi, w, masks, af)
     return GruSequence.apply(gi, w, masks, af)
 
 
