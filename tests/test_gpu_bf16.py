@@ -267,8 +267,9 @@ def test_pack_bf16(ops):
                                        (128, 100, 310, 510, 2), (17, 37, 128, 256, 2)])
 @pytest.mark.parametrize("form", ["fold", "rgemm"])
 def test_lowrank_bilinear_fusion_bf16(ops, B, N, L, H, R, form, monkeypatch):
-    """both forms of the bf16 K4: rank-folded (csrc/bilinear_fold_bf16.hip, the default where R = 2 and N <= 128) and R GEMMs
-    (csrc/bf16_path.hip) -- against the float64 closed forms on bf16-rounded operands"""
+    """both forms of the bf16 K4: R GEMMs (csrc/bf16_path.hip, the default: ops.K4_BF16_FORM = "rgemm") and rank-folded
+    (csrc/bilinear_fold_bf16.hip, VQA_K4_BF16_FORM=fold, taken where R = 2 and N <= 128) -- against the float64 closed forms on
+    bf16-rounded operands"""
     monkeypatch.setattr(ops, "K4_BF16_FORM", form)
     Lp = ops.pad_to(L)
     x = bf_round(seeded.seeded_array((B, N, L), 251))

@@ -488,9 +488,14 @@ def test_cor2_eval_logits_with_the_bf16_encoder(measured):
 
 
 @gpu
-def test_cor2_trains_and_evaluates_under_graph_replay_with_the_bf16_encoder():
+def test_cor2_trains_and_evaluates_under_graph_replay_with_the_bf16_encoder(lib_option):
     from vqa_playground_pytorch_amd.evaluate import Evaluator
     from vqa_playground_pytorch_amd.trainer import DataParallelTrainer
+    # MB = 8 is below the batch from which the attention-pool backward takes its one-launch form (VQA_K3_FUSED_MIN_B: 64 for fp32
+    # regions); the three-launch form below it adds its partial sums with float atomics in arrival order, so two runs of this step
+    # differed in the last bits of the loss now and then (tests/test_gpu_models.py::test_step_is_bitwise_reproducible_...).  The
+    # run-to-run check below is about the recurrent path: take the fixed-order form, as tests/test_gpu_kernels.py does.
+    lib_option("VQA_K3_FUSED_MIN_B", 1)
     sample, a = _batch()
     losses = []
     for _ in range(2):
