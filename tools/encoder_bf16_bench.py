@@ -1,15 +1,19 @@
-"""The question encoder's mixed-precision recurrent path next to the fp32 one, as ONE JSON line on stdout.
+"""The question encoder's mixed-precision modes next to the fp32 one, as ONE JSON line on stdout.
 
     python tools/encoder_bf16_bench.py [--batch 512] [--blocks 6] [--skip-step]
 
-Everything is timed on one GPU in one call, in alternating blocks (fp32, bf16, bf16, fp32, ...), so drift of the clock hits both
-sides alike; every figure is the median of its blocks, the blocks themselves are in the record.
+Everything is timed on one GPU in one call, in alternating blocks (fp32, bf16, bf16+in, bf16+in, bf16, fp32, ...), so drift of the
+clock hits all sides alike; every figure is the median of its blocks, the blocks themselves are in the record.  The encoder and the
+step are timed in three modes: f32, bf16 (compute_dtype=bf16: the recurrent products) and bf16_in (compute_dtype=bf16 plus
+input_dtype=bf16: the input side too, csrc/encoder_input_bf16.hip).
 
 product   the per-step recurrent product 3 x [B,2400] x [2400,2400]^T: vqa_gemm_nt_split_batched (fp32 operands, six bf16
           partial products) and vqa_gru_gemm_bf16 (one bf16 product), us per launch and TFLOP/s of the 2 G M N K operations
 dw        the recurrent weight gradient over all T*B rows: three vqa_gemm_tn_split against three vqa_gemm_bf16_tn
 encoder   SkipThoughts forward + backward alone (B x 26 tokens, lengths 5..26, training mode), ms
 step      the graph-replayed CoR2 train step with the encoder in it (bench.py --encoder's workload), ms per step
+input     per-launch times (KernelTimer: an event pair around each launch) of what the encoder's input side launches over its
+          B*T rows in the bf16 and bf16_in modes: the split engine's products, or the three new kernels and the bf16 products
 history   bytes of one [3,T,B,.] GEMM-operand history before and after
 bench.py --encoder is the headline measurement and is unchanged (VQA_ENCODER_DTYPE=bf16 selects the mode there; its line does
 not say which encoder ran)."""
@@ -60,7 +64,9 @@ def summary(blocks, flops=None):
         if flops:
             rec[name]["tflops"] = round(flops / med / 1e9, 1)
     names = list(blocks)
-    rec["ratio_%s_over_%s" % (names[0], names[1])] = round(rec[names[0]]["ms"] / rec[names[1]]["ms"], 3)
+    for a, b in zip(names, names[1:]):
+        rec["ratio_%s_over_%s" % (a, b)] = round(rec[a]["ms"] / rec[b]["ms"], 3)
+        rec["ranges_overlap_%s_%s" % (a, b)] = bool(min(blocks[a]) <= max(blocks[b]) and min(blocks[b]) <= max(blocks[a]))
     return rec
 
 
@@ -113,22 +119,40 @@ def tokens(B, vocab, dev, seed):
     return q.to(dev)
 
 
+MODES = (("f32", None, None), ("bf16", torch.bfloat16, None), ("bf16_in", torch.bfloat16, torch.bfloat16))
+INPUT_KERNELS = ("embed_pack_bf16", "gemm_bf16_nt_f32_bias", "embed_grad", "gemm_bf16_tn", "gru_gemm_bf16", "pack_bf16", "column_sum",
+                 "gemm_nt_split_batched", "gemm_tn_split", "bias_act", "act_bwd_colsum")
+
+
 def encoder(args, dev):
+    from vqa_playground_pytorch_amd import ops
     from vqa_playground_pytorch_amd.encoder import SkipThoughts
     vocab = ["PAD", "UNK"] + ["w%d" % i for i in range(14998)]
     q = tokens(args.batch, len(vocab), dev, 2)
     gy = torch.randn(args.batch, H, generator=torch.Generator().manual_seed(3)).to(dev)
     forms = {}
-    for name, dtype in (("f32", None), ("bf16", torch.bfloat16)):
+    for name, dtype, in_dtype in MODES:
         torch.manual_seed(4)
-        m = SkipThoughts(vocab, af="relu", compute_dtype=dtype).to(dev).train()
+        m = SkipThoughts(vocab, af="relu", compute_dtype=dtype, input_dtype=in_dtype).to(dev).train()
 
         def run(m=m):
             for prm in m.parameters():
                 prm.grad = None
             m(q).backward(gy)
         forms[name] = run
-    return summary(alternate(forms, args.blocks, max(args.iters // 10, 2), warmup=2))
+    rec = summary(alternate(forms, args.blocks, max(args.iters // 10, 2), warmup=2))
+    # per-launch times of the input side's launches (those over all B*T rows), three passes each
+    M, launches = args.batch * T, {}
+    for name in ("bf16", "bf16_in"):
+        timer = ops.KernelTimer(INPUT_KERNELS)
+        ops.set_kernel_timer(timer)
+        for _ in range(3):
+            forms[name]()
+        torch.cuda.synchronize()
+        ops.set_kernel_timer(None)
+        launches[name] = {"%s %s" % (k, list(shape)): {"launches_per_pass": n // 3, "us": round(ms * 1e3, 1)}
+                          for (k, shape), (n, ms) in sorted(timer.summary().items()) if M in shape or (args.batch in shape and T in shape)}
+    return rec, launches
 
 
 def step(args, dev):
@@ -140,9 +164,10 @@ def step(args, dev):
     sample = {"v": torch.randn(B, 36, 2048, generator=gen).to(dev), "q_idxes": tokens(B, len(vocab), dev, 6)}
     a = torch.softmax(2.0 * torch.randn(B, C, generator=gen), 1).to(dev)
     forms, nodes = {}, {}
-    for name, dtype in (("f32", torch.float32), ("bf16", torch.bfloat16)):
+    for name, dtype, in_dtype in MODES:
         torch.manual_seed(1234)
-        model = CoR2Model(vocab, C, seq2vec="skipthoughts", encoder_dtype=dtype).to(dev).train()
+        model = CoR2Model(vocab, C, seq2vec="skipthoughts", encoder_dtype=dtype or torch.float32,
+                          encoder_input_dtype=in_dtype or torch.float32).to(dev).train()
         tr = DataParallelTrainer(model, lr=1e-4, clip=0.25, graph=True, adopt_inputs=True)
         for _ in range(6):
             tr.step(sample, a)
@@ -152,7 +177,7 @@ def step(args, dev):
         nodes[name] = tr.graph_nodes
         forms[name] = lambda tr=tr: tr.step(sample, a)
     rec = summary(alternate(forms, args.blocks, max(args.iters // 5, 3), warmup=2))
-    for name in ("f32", "bf16"):
+    for name, _, _ in MODES:
         rec[name]["samples_per_s"] = round(B / rec[name]["ms"] * 1e3, 1)
     rec["graph_nodes"] = nodes
     return rec
@@ -171,7 +196,7 @@ def main():
     B, Hp = args.batch, ops.pad_to(H)
     rec = {"tool": "encoder_bf16_bench", "batch": B, "T": T, "H": H}
     rec["product"], rec["dw"] = product(args, dev)
-    rec["encoder_fwd_bwd"] = encoder(args, dev)
+    rec["encoder_fwd_bwd"], rec["input"] = encoder(args, dev)
     if not args.skip_step:
         rec["step"] = step(args, dev)
     rec["history_bytes"] = {"f32": 3 * T * B * H * 4, "bf16": 3 * T * B * Hp * 2}

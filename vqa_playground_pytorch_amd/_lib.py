@@ -150,6 +150,10 @@ SIGNATURES = {
                                       _c_i, _c_i, _c_i, _c_i, _c_i, _c_st]),
     "vqa_gru_gates_bwd_bf16": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_sz, _c_i, _c_f, _c_f,
                                       _c_i, _c_i, _c_i, _c_i, _c_i, _c_st]),
+    "vqa_embed_pack_bf16": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_st]),
+    "vqa_gemm_bf16_nt_f32_bias": (_c_i, [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_l, _c_f, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i,
+                                         _c_st]),
+    "vqa_embed_grad": (_c_i, [_c_f, _c_l, _c_i, _c_f, _c_f, _c_l, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_st]),
     "vqa_bias_act": (_c_i, [_c_f, _c_f, _c_i, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_st]),
     "vqa_act_bwd_colsum": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_st]),
     "vqa_column_sum_workspace_bytes": (_c_sz, [_c_i, _c_i]),

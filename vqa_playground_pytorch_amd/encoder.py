@@ -25,7 +25,9 @@ def _af(name):
 class _RecurrentProductBf16(torch.autograd.Function):
     """a = bf(hm) bf(W)^T with the backward of the mixed-precision contract (csrc/gru_bf16.hip) in torch ops: the incoming gradient
     is rounded to bf16 for the two products it feeds, d_hm = bf(g) bf(W) and d_W = bf(g)^T bf(hm); the roundings themselves are
-    straight-through.  Operands keep their dtype (the bf16 VALUES in fp32 / fp64 storage), so the products accumulate in it."""
+    straight-through.  Operands keep their dtype (the bf16 VALUES in fp32 / fp64 storage), so the products accumulate in it.
+    The input side's contract (csrc/encoder_input_bf16.hip) is the same function of (x * mx_g, W_ig): input_dtype=bfloat16 uses it
+    for the three input projections."""
 
     @staticmethod
     def forward(ctx, hm, w):
@@ -59,11 +61,15 @@ class BayesianGRU(nn.Module):
     (SequentialDropout); ``forward(x [B,T,in], lengths [B]) -> [B,hidden]`` = the state at step lengths-1."""
 
     def __init__(self, input_size, hidden_size, bias_ih=True, bias_hh=False, dropout=0.25, return_last=True, af="tanh",
-                 compute_dtype=None):
+                 compute_dtype=None, input_dtype=None):
         super().__init__()
         # torch.bfloat16: the recurrent products in mixed precision (bf16 operands, fp32 accumulation; csrc/gru_bf16.hip states
         # the contract, INTEGRATION.md section 2).  Parameters, state and the input side stay fp32 either way.
         self.compute_dtype = ops.parse_compute_dtype(compute_dtype)
+        # torch.bfloat16: the INPUT side in mixed precision -- the embedded input (times its dropout mask) and the three input
+        # weights rounded to bf16, fp32 accumulation, fp32 gi and biases (csrc/encoder_input_bf16.hip states the contract).  A
+        # switch of its own: either value combines with either compute_dtype.
+        self.input_dtype = ops.parse_compute_dtype(input_dtype, "input_dtype")
         self.input_size, self.hidden_size = input_size, hidden_size
         self.dropout, self.return_last, self.af = dropout, return_last, af
         self.gru_cell = BayesianGRUCell(input_size, hidden_size, bias_ih, bias_hh, dropout=dropout, af=af)
@@ -81,6 +87,38 @@ class BayesianGRU(nn.Module):
         if inp[0].bias is not None:
             groups.append([m.bias for m in inp])
         return groups
+
+    def _takes_hip(self, is_cuda):
+        # (the mixed-precision modes never fall back to fp32 products: a width their kernels do not take raises in ops)
+        mixed = torch.bfloat16 in (self.compute_dtype, self.input_dtype)
+        return bool(is_cuda and self.af in ("relu", "tanh") and self.gru_cell.weight_hr.bias is None
+                    and (mixed or self.hidden_size % 4 == 0))
+
+    def _forward_hip_input_bf16(self, x, lengths, table, padding_idx):
+        """_forward_hip with the input side in mixed precision: ops.encoder_input_bf16 instead of the masked copy of the input and
+        the batched fp32 GEMM.  x: the token ids [B,T] when `table` (the embedding's weight) is given -- the lookup then happens
+        inside the pack kernel --, else the float input [B,T,K].  The six masks are drawn in the order of the fp32 path."""
+        c = self.gru_cell
+        inp, hid = (c.weight_ir, c.weight_ii, c.weight_in), (c.weight_hr, c.weight_hi, c.weight_hn)
+        B, T = x.shape[:2]
+        like = table if table is not None else x
+        mx = mh = None
+        if self.training and self.dropout > 0:
+            proto = like.new_empty(B, 1, self.input_size)
+            mx = torch.stack([self._mask(proto) for _ in range(3)], 2).view(B, 3, self.input_size)       # shared over time
+            mh = torch.stack([self._mask(like.new_zeros(B, self.hidden_size)) for _ in range(3)])       # [3,B,H]
+        w_in = ops.stack_params([m.weight for m in inp])
+        b_in = ops.stack_params([m.bias for m in inp]) if inp[0].bias is not None else None
+        if table is not None:
+            gi = ops.encoder_input_bf16(table, x, mx, w_in, b_in, padding_idx)
+        else:
+            gi = ops.encoder_input_bf16(x, None, mx, w_in, b_in)
+        out = ops.gru_sequence(gi, ops.stack_params([m.weight for m in hid]), mh, self.af, self.compute_dtype)      # [T,B,H]
+        if not self.return_last:
+            return out.transpose(0, 1)
+        self.all_hiddens = out.detach().transpose(0, 1)
+        idx = (lengths.long() - 1) % T
+        return out[idx, torch.arange(B, device=x.device)]
 
     def _forward_hip(self, x, lengths):
         """GPU form: the three input projections of all T steps as one batched GEMM, then ops.GruSequence (per step one
@@ -105,10 +143,17 @@ class BayesianGRU(nn.Module):
         idx = (lengths.long() - 1) % T
         return out[idx, torch.arange(B, device=x.device)]
 
-    def forward(self, x, lengths=None):
+    def forward(self, x, lengths=None, table=None, padding_idx=None):
+        """table (+ padding_idx): SkipThoughts' way into the mixed-precision input side on the GPU -- x is then the int64 token
+        ids [B,T] and `table` the embedding's weight (only with input_dtype=bfloat16 on a device _takes_hip accepts)."""
         c, af = self.gru_cell, _af(self.af)
-        B, T, _ = x.shape
         bf16 = self.compute_dtype == torch.bfloat16
+        in_bf16 = self.input_dtype == torch.bfloat16
+        if table is not None and not (in_bf16 and self._takes_hip(x.is_cuda)):
+            raise ValueError("BayesianGRU: token ids with a table are taken by the input_dtype=bfloat16 GPU path only")
+        if in_bf16 and self._takes_hip(x.is_cuda):
+            return self._forward_hip_input_bf16(x, lengths, table, padding_idx)
+        B, T, _ = x.shape
         # (the mixed-precision mode never falls back to fp32 products: a width its kernels do not take raises in ops.gru_sequence)
         if x.is_cuda and self.af in ("relu", "tanh") and c.weight_hr.bias is None and (bf16 or self.hidden_size % 4 == 0):
             return self._forward_hip(x, lengths)
@@ -121,8 +166,14 @@ class BayesianGRU(nn.Module):
         mx = [self._mask(x[:, :1, :]) for _ in range(3)]                       # [B,1,in], shared over time
         h = x.new_zeros(B, self.hidden_size)
         mh = [self._mask(h) for _ in range(3)]                                 # [B,hidden]
-        gi = [ops.linear(x if m is None else x * m, lin.weight, lin.bias)                # (replay-safe bias gradient)
-              for lin, m in zip((c.weight_ir, c.weight_ii, c.weight_in), mx)]
+        if in_bf16:                    # gi_g = bf(x m_g) bf(W_ig)^T + b_g: the input side's contract (csrc/encoder_input_bf16.hip)
+            gi = []
+            for lin, m in zip((c.weight_ir, c.weight_ii, c.weight_in), mx):
+                g = _RecurrentProductBf16.apply((x if m is None else x * m).reshape(B * T, -1), lin.weight).view(B, T, -1)
+                gi.append(g if lin.bias is None else g + lin.bias)
+        else:
+            gi = [ops.linear(x if m is None else x * m, lin.weight, lin.bias)                # (replay-safe bias gradient)
+                  for lin, m in zip((c.weight_ir, c.weight_ii, c.weight_in), mx)]
         outs = []
         for t in range(T):
             hr, hi, hn = (h if m is None else h * m for m in mh)
@@ -150,19 +201,31 @@ def encoder_dtype_from(encoder_dtype):
     return torch.bfloat16 if env == "bf16" else torch.float32
 
 
+def encoder_input_dtype_from(encoder_input_dtype):
+    """encoder_dtype_from for the encoder's INPUT side: the caller's ``encoder_input_dtype`` (validated), or, when that is None,
+    the environment variable VQA_ENCODER_INPUT_DTYPE (``f32``, the default, or ``bf16``)."""
+    if encoder_input_dtype is not None:
+        return ops.parse_compute_dtype(encoder_input_dtype, "encoder_input_dtype")
+    env = os.environ.get("VQA_ENCODER_INPUT_DTYPE", "f32")
+    if env not in ("f32", "bf16"):
+        raise ValueError("VQA_ENCODER_INPUT_DTYPE must be f32 or bf16, got %r" % (env,))
+    return torch.bfloat16 if env == "bf16" else torch.float32
+
+
 class SkipThoughts(nn.Module):
     """putils/__init__.py:878-985: ``forward(q_idxes int64 [B,T], 0 = PAD) -> [B,2400]``."""
 
     def __init__(self, vocab_list, data_dir=None, gru="BayesianGRU", return_last=True, af="tanh", pretrained=None,
-                 compute_dtype=None):
+                 compute_dtype=None, input_dtype=None):
         super().__init__()
         if gru != "BayesianGRU":
             raise ValueError("only the BayesianGRU encoder of config/CoR2.py:166 / config/ODA.py:183 is provided")
         self.vocab_list, self.data_dir, self.af = vocab_list, data_dir, af
         self.embedding = nn.Embedding(num_embeddings=len(vocab_list), embedding_dim=620, padding_idx=0)
         self.gru = BayesianGRU(input_size=620, hidden_size=2400, dropout=0.25, return_last=return_last, af=af,
-                               compute_dtype=compute_dtype)
+                               compute_dtype=compute_dtype, input_dtype=input_dtype)
         self.compute_dtype = self.gru.compute_dtype
+        self.input_dtype = self.gru.input_dtype
         if pretrained is not None:
             self.load_pretrained(pretrained)
 
@@ -188,6 +251,11 @@ class SkipThoughts(nn.Module):
     def forward(self, x, return_hidden=False):
         if x.dtype != torch.long:
             raise ValueError("SkipThoughts expects int64 token ids [B,T] (0 = PAD)")
+        if self.input_dtype == torch.bfloat16 and self.gru._takes_hip(x.is_cuda):
+            # the lookup, the input masks and the bf16 rounding are one kernel there: no fp32 [B,T,620] tensor
+            lengths = x.size(1) - x.eq(0).sum(1)
+            out = self.gru(x, lengths, table=self.embedding.weight, padding_idx=self.embedding.padding_idx)
+            return (out, self.gru.all_hiddens) if return_hidden else out
         emb = ops.embedding(self.embedding.weight, x, self.embedding.padding_idx) if x.is_cuda else self.embedding(x)
         lengths = x.size(1) - x.eq(0).sum(1)
         out = self.gru(emb, lengths)

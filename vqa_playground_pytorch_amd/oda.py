@@ -14,20 +14,22 @@ from .layers import MutanFusion, MyATT, MyConv1d, MyLinear, QuestionVectorInput,
 
 
 class Model(nn.Module):
-    def __init__(self, vocab_words=None, num_ans=None, seq2vec=None, regions=36, encoder_dtype=None):
+    def __init__(self, vocab_words=None, num_ans=None, seq2vec=None, regions=36, encoder_dtype=None, encoder_input_dtype=None):
         super().__init__()
         self.vocab_words = vocab_words
         self.num_classes = num_ans
         self.regions = regions
 
         if seq2vec == "skipthoughts":      # the reference's encoder (config/CoR2.py:166), randomly initialised here
-            from .encoder import SkipThoughts, encoder_dtype_from
+            from .encoder import SkipThoughts, encoder_dtype_from, encoder_input_dtype_from
             seq2vec = SkipThoughts(vocab_list=vocab_words, gru="BayesianGRU", return_last=True, af="relu",
-                                   compute_dtype=encoder_dtype_from(encoder_dtype))
-        elif encoder_dtype is not None:
+                                   compute_dtype=encoder_dtype_from(encoder_dtype),
+                                   input_dtype=encoder_input_dtype_from(encoder_input_dtype))
+        elif encoder_dtype is not None or encoder_input_dtype is not None:
             given = seq2vec if seq2vec is None or isinstance(seq2vec, str) else type(seq2vec).__name__
-            raise ValueError("encoder_dtype configures the SkipThoughts encoder that seq2vec='skipthoughts' builds; "
-                             "it cannot be given with seq2vec=%r" % (given,))
+            raise ValueError("%s configures the SkipThoughts encoder that seq2vec='skipthoughts' builds; "
+                             "it cannot be given with seq2vec=%r"
+                             % ("encoder_dtype" if encoder_dtype is not None else "encoder_input_dtype", given))
         if seq2vec == "vector":             # explicit pass-through slot: sample['q_idxes'] holds the 2400-d question vector
             seq2vec = None
         self.seq2vec = seq2vec if seq2vec is not None else QuestionVectorInput(2400)

@@ -1818,6 +1818,118 @@ def gru_sequence(gi, w, masks, af, compute_dtype=None):
     return GruSequence.apply(gi, w, masks, af)
 
 
+def _pack_stack_bf16(w, dst, batch_stride, row_stride, col_stride):
+    """vqa_pack_bf16 of a stack [G,rows,cols] of fp32 masters into `dst`: one launch when the stack is dense, one per member
+    when its members are spaced apart (stack_params' view of a flat parameter buffer) -- never a dense copy of the masters."""
+    if w.is_contiguous():
+        return pack_bf16(w, dst, batch_stride, row_stride, col_stride, zero_fill=False)
+    for g in range(w.shape[0]):
+        pack_bf16(w[g], dst, 0, row_stride, col_stride, zero_fill=False, offset=g * batch_stride)
+    return dst
+
+
+class EncoderInputBf16(torch.autograd.Function):
+    """The input side of the BayesianGRU in mixed precision (csrc/encoder_input_bf16.hip states the contract): gi_g = bf(e mx_g)
+    bf(W_ig)^T + b_g for the three gates and all B*T rows, fp32 accumulation, fp32 gi [3,B,T,H] -- what gru_sequence takes.
+    src: the embedding table [V,K] with idx int64 [B,T] (the lookup is part of the pack kernel: no fp32 [B,T,K] tensor), or
+    x [B,T,K] with idx None; mx [B,3,K] sequence-shared input masks or None; w_in [3,H,K] fp32 masters; b_in [3,H] or None.
+    Forward: vqa_pack_bf16 (weight shadow), vqa_embed_pack_bf16, vqa_gemm_bf16_nt_f32_bias.  Backward: vqa_column_sum x 3 (the
+    unrounded d_gi), vqa_pack_bf16 (dgb = bf(d_gi)), vqa_gemm_bf16_tn_ex x 3 (d_w, written master-shaped), and for the data
+    gradient vqa_pack_bf16 (transposed shadow), vqa_gru_gemm_bf16, vqa_embed_grad.  Needs K % 4 == 0 and H % 8 == 0."""
+
+    @staticmethod
+    def forward(ctx, src, idx, mx, w_in, b_in, padding_idx):
+        src = _prep("table_or_x", src)
+        if not (isinstance(w_in, torch.Tensor) and w_in.is_cuda and w_in.dtype == torch.float32 and w_in.dim() == 3
+                and w_in.shape[0] == 3 and w_in[0].is_contiguous()):
+            raise ValueError("encoder_input_bf16: w_in must be a CUDA fp32 stack [3,H,K] of dense members")
+        _, H, K = w_in.shape
+        if idx is not None:
+            if idx.dtype != torch.int64 or idx.dim() != 2 or not idx.is_cuda or src.dim() != 2 or src.shape[1] != K:
+                raise ValueError("encoder_input_bf16: with idx (CUDA int64 [B,T]) the first argument is the table [V,%d]" % K)
+            idx = idx.contiguous()
+            B, T = idx.shape
+            V = src.shape[0]
+        else:
+            if src.dim() != 3 or src.shape[2] != K:
+                raise ValueError("encoder_input_bf16: x must be [B,T,%d], got %s" % (K, tuple(src.shape)))
+            B, T, _ = src.shape
+            V = 0
+        if K % 4 or H % 8:
+            raise ValueError("encoder_input_bf16: needs an input size that is a multiple of 4 and a hidden size that is a multiple "
+                             "of 8, got K = %d, H = %d" % (K, H))
+        if mx is not None:
+            mx = _prep("mx", mx)
+            if mx.shape != (B, 3, K):
+                raise ValueError("encoder_input_bf16: mx must be [B,3,K] = [%d,3,%d], got %s" % (B, K, tuple(mx.shape)))
+        if b_in is not None and (b_in.shape != (3, H) or b_in.dtype != torch.float32 or b_in.stride(1) != 1):
+            raise ValueError("encoder_input_bf16: b_in must be fp32 [3,%d] with contiguous rows" % H)
+        dev, M, Kp, L_ = src.device, B * T, pad_to(K), _lib.lib()
+        planes = 3 if mx is not None else 1
+        xb = torch.empty(planes, M, Kp, device=dev, dtype=torch.bfloat16)      # xb_g = bf(e * mx_g); the pads zeroed once, here
+        wb = torch.empty(3, H, Kp, device=dev, dtype=torch.bfloat16)           # Wb_g = bf(W_ig)
+        if Kp > K:
+            xb[:, :, K:].zero_()
+            wb[:, :, K:].zero_()
+        _pack_stack_bf16(w_in, wb, H * Kp, Kp, 1)
+        _launch("embed_pack_bf16", (B, T, K, planes), L_.vqa_embed_pack_bf16, _p(src), _p(idx), _p(mx), _p(xb), M * Kp, Kp, M, K, T,
+                V, 3)
+        gi = torch.empty(3, B, T, H, device=dev, dtype=torch.float32)
+        _launch("gemm_bf16_nt_f32_bias", (3, M, H, K), L_.vqa_gemm_bf16_nt_f32_bias, _p(xb), M * Kp if planes == 3 else 0, Kp,
+                _p(wb), H * Kp, Kp, _p(b_in), b_in.stride(0) if b_in is not None else 0, _p(gi), M * H, H, 3, M, H, K)
+        ctx.save_for_backward(xb, idx, mx, w_in, src if idx is not None else None)
+        ctx.bias = b_in
+        ctx.cfg = (B, T, K, H, V, tuple(src.shape), -1 if padding_idx is None else int(padding_idx))
+        return gi
+
+    @staticmethod
+    def backward(ctx, d_gi):
+        xb, idx, mx, w_in, table = ctx.saved_tensors
+        B, T, K, H, V, src_shape, padding_idx = ctx.cfg
+        d_gi = _prep("grad_out", d_gi)
+        dev, M, Kp, Hp, L_ = d_gi.device, B * T, pad_to(K), pad_to(H), _lib.lib()
+        planes = xb.shape[0]
+        g2 = d_gi.view(3, M, H)
+        d_b = None
+        if ctx.bias is not None and ctx.needs_input_grad[4]:       # the column sums of the UNROUNDED d_gi
+            d_b = _grad_like(ctx.bias, rows_strided=True)
+            for g in range(3):
+                column_sum(g2[g], out=d_b[g])
+        dgb = torch.empty(3, M, Hp, device=dev, dtype=torch.bfloat16)          # dgb = bf(d_gi), rows padded for the data gradient
+        if Hp > H:
+            dgb[:, :, H:].zero_()
+        pack_bf16(g2, dgb, M * Hp, Hp, 1, zero_fill=False)
+        d_w = None
+        if ctx.needs_input_grad[3]:
+            # d_w[g] = dgb_g^T xb_g over all M rows, the padded columns cropped: straight into the master-shaped gradient
+            d_w = _grad_like(w_in)
+            ws_bytes = L_.vqa_gemm_bf16_tn_workspace_bytes(M, H, Kp)
+            ws = torch.empty((ws_bytes + 3) // 4, device=dev, dtype=torch.float32)
+            for g in range(3):
+                _launch("gemm_bf16_tn", (M, H, Kp), L_.vqa_gemm_bf16_tn_ex, ctypes.c_void_p(dgb.data_ptr() + 2 * g * M * Hp), Hp,
+                        ctypes.c_void_p(xb.data_ptr() + 2 * (g if planes == 3 else 0) * M * Kp), Kp, _ptr_array([d_w[g]]), 1, H, H,
+                        K, K, _p(ws), ws_bytes, M, H, Kp, 0.0, 0, None)
+        d_src = None
+        if ctx.needs_input_grad[0]:
+            Kx = pad_to(K, 8)                                                  # the product's N: K padded to a multiple of 8
+            wbt = torch.zeros(3, Kx, Hp, device=dev, dtype=torch.bfloat16)     # Wb_g^T; rows [K, Kx) and the pads stay zero
+            _pack_stack_bf16(w_in, wbt, Kx * Hp, 1, Hp)
+            dxm = torch.empty(3, M, Kx, device=dev, dtype=torch.float32)
+            gru_gemm_bf16(dgb, 0, M * Hp, Hp, wbt, Kx * Hp, Hp, dxm, 3, M, Kx, H)                              # dxm_g = dgb_g Wb_g
+            # the table's gradient is scattered with atomic adds into a zero-filled slot (a fill kernel, as EmbeddingFn.backward's
+            # torch.zeros: never a memset node in a captured step); the dense form is plain stores
+            d_src = _grad_like(table).zero_() if idx is not None else torch.empty(src_shape, device=dev, dtype=torch.float32)
+            _launch("embed_grad", (B, T, K, int(idx is not None)), L_.vqa_embed_grad, _p(dxm), M * Kx, Kx, _p(mx), _p(idx),
+                    padding_idx, _p(d_src), M, K, T, V, 3)
+        return d_src, None, None, d_w, d_b, None
+
+
+def encoder_input_bf16(table_or_x, idx, mx, w_in, b_in=None, padding_idx=None):
+    """gi [3,B,T,H] of the BayesianGRU's input side in mixed precision: EncoderInputBf16.  padding_idx: the token id whose
+    table row gets no gradient (nn.Embedding's padding_idx); without idx it is ignored."""
+    return EncoderInputBf16.apply(table_or_x, idx, mx, w_in, b_in, padding_idx)
+
+
 class EmbeddingFn(torch.autograd.Function):
     """nn.Embedding lookup whose backward is a zero-filled table + index_add_ (atomic adds): torch's own
     embedding_dense_backward issues a memset, which must not sit inside a replayed hipGraph (csrc/api.hip)."""
