@@ -24,6 +24,7 @@
 namespace vqa {
 
 constexpr int kMaxG = 8;
+constexpr size_t kMaxLds = 160 * 1024;   // LDS of a gfx950 CU: the most one workgroup can ask for
 
 // softmax over n for every glimpse; logits_b -> alpha_s (LDS, [N][G]).  Called by all NT threads.
 template <int NT>
@@ -368,7 +369,9 @@ static int launch_bwd(const float* alpha, const T* v, const float* d_pooled, con
     // and this form sums in a fixed order, the other one with float atomics); bf16 regions from 512 (N = 100, B = 128: +2 %)
     const int min_b = env != nullptr ? std::atoi(env) : (sizeof(T) == 4 ? 64 : 512);
     const size_t lds_f = ((size_t)(2 + NT / 64) * N * G + kMaxG) * sizeof(float);
-    if (B >= min_b && D % 4 == 0 && D <= 4 * NT * 2 && D > 4 * NT) {
+    // (its LDS grows with N G: 196 640 bytes at N = 1024, G = 8 -- more than a CU has; such a sample takes the three-launch form)
+    if (B >= min_b && D % 4 == 0 && D <= 4 * NT * 2 && D > 4 * NT && lds_f <= kMaxLds) {
+      if (lds_f > 65536) VQA_ENSURE_LDS((attention_pool_bwd_fused_kernel<T, NT, G, 2>), lds_f);
       VQA_LAUNCH((attention_pool_bwd_fused_kernel<T, NT, G, 2>), dim3(B), dim3(NT), lds_f, s, alpha, v, d_pooled, d_first,
                          d_alpha_ext, d_logits, d_v, N, D, dc);
       return check_launch("softmax_attention_pool_bwd");
@@ -387,7 +390,9 @@ static int launch_bwd(const float* alpha, const T* v, const float* d_pooled, con
     VQA_LAUNCH((attention_pool_bwd_stream_kernel<T, NT, G, 1>), dim3((D / 4 + NT - 1) / NT, B), dim3(NT), lds, s, alpha,
                        v, d_pooled, d_first, d_logits, d_v, N, D, dc);
   }
-  VQA_LAUNCH(attention_softmax_bwd_kernel, dim3(B), dim3(256), lds + kMaxG * sizeof(float), s, alpha, d_logits,
+  const size_t lds_s = lds + kMaxG * sizeof(float);   // 65 568 bytes at N = 1024, G = 8 (the stream kernels' 2 N G floats: 64 KiB at most)
+  if (lds_s > 65536) VQA_ENSURE_LDS(attention_softmax_bwd_kernel, lds_s);
+  VQA_LAUNCH(attention_softmax_bwd_kernel, dim3(B), dim3(256), lds_s, s, alpha, d_logits,
                      d_alpha_ext, d_logits, N, G);
   return check_launch("softmax_attention_pool_bwd");
 }
