@@ -911,3 +911,46 @@ def test_gru_sequence_at_full_width_and_length(ops, monkeypatch, measured):
     seen, bmms = _sequence_case(ops, monkeypatch, measured, 100, 26, 620, 2400, "tanh", True, "B=100 T=26 full width")
     _assert_path(seen, bmms, 100, 26, batched=True)
     assert [n for n, _ in seen].count("gemm_tn_split") == 6
+
+
+# ---- 6. the launches of one sequence, in order ----------------------------------------------------------------------------------
+def _launch_steps(first, product, gate, T):
+    """[first, gate] + [product, gate] * (T - 1): what is prepared once per pass, then a gate launch per step with the step's
+    product in front of all but the first"""
+    return [first, gate] + [product, gate] * (T - 1)
+
+
+# Recorded from ops.GruSequence / ops.GruSequenceBf16 as they stood before the two shared one loop body (forward then backward, relu,
+# masks given, d_w wanted); (compute_dtype, B, T, H) -> names handed to ops._launch.  fp32: B = 2 takes the grouped fallback (every
+# product one direct-output grouped launch), B = 64, H = 324 the batched kernel (the smallest such case of section 5; 324 is outside
+# of vqa_gemm_tn_split: d_w is a grouped launch on the split engine with its epilogue).  bf16 has one path; H = 328 is 324 rounded
+# up to the multiple of 8 it needs.
+GRU_LAUNCHES = {
+    (None, 2, 3, 8): ["gru_gates_fwd", "grouped_gemm", "gru_gates_fwd", "grouped_gemm", "gru_gates_fwd",
+                      "gru_gates_bwd", "grouped_gemm", "gru_gates_bwd", "grouped_gemm", "gru_gates_bwd", "grouped_gemm"],
+    (None, 64, 9, 324): _launch_steps("split_weights_pack", "gemm_nt_split_batched", "gru_gates_fwd", 9)
+    + _launch_steps("split_weights_pack", "gemm_nt_split_batched", "gru_gates_bwd", 9) + ["grouped_gemm_split", "grouped_epilogue"],
+    ("bf16", 2, 3, 8): ["pack_bf16", "gru_gates_fwd_bf16", "gru_gemm_bf16", "gru_gates_fwd_bf16", "gru_gemm_bf16", "gru_gates_fwd_bf16",
+                        "pack_bf16", "gru_gates_bwd_bf16", "gru_gemm_bf16", "gru_gates_bwd_bf16", "gru_gemm_bf16", "gru_gates_bwd_bf16",
+                        "gemm_bf16_tn", "gemm_bf16_tn", "gemm_bf16_tn"],
+    ("bf16", 64, 9, 328): _launch_steps("pack_bf16", "gru_gemm_bf16", "gru_gates_fwd_bf16", 9)
+    + _launch_steps("pack_bf16", "gru_gemm_bf16", "gru_gates_bwd_bf16", 9) + ["gemm_bf16_tn"] * 3,
+}
+
+
+@gpu
+@pytest.mark.parametrize("case", list(GRU_LAUNCHES), ids=lambda c: "%s-B%dT%dH%d" % (c[0] or "f32", *c[1:]))
+def test_gru_sequence_issues_the_recorded_launches_in_order(ops, monkeypatch, case):
+    dtype, B, T, H = case
+    gen = torch.Generator().manual_seed(B + H)
+    gi = (0.5 * torch.randn(3, B, T, H, generator=gen)).to(dev()).requires_grad_()
+    w = (torch.randn(3, H, H, generator=gen) / H ** 0.5).to(dev()).requires_grad_()
+    masks = ((torch.rand(3, B, H, generator=gen) > 0.25).float() / 0.75).to(dev())
+    seen, inner = [], ops._launch
+    monkeypatch.setattr(ops, "_launch", lambda name, shape, *a, **k: (seen.append(name), inner(name, shape, *a, **k))[1])
+    out = ops.gru_sequence(gi, w, masks, "relu", compute_dtype=dtype)
+    out.backward(torch.randn(T, B, H, generator=gen).to(dev()))
+    torch.cuda.synchronize()
+    monkeypatch.setattr(ops, "_launch", inner)
+    assert seen == GRU_LAUNCHES[case], seen
+    assert all(bool(torch.isfinite(t).all()) for t in (out, gi.grad, w.grad))

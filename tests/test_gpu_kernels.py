@@ -217,6 +217,35 @@ def test_softmax_attention_pool_backward_single_launch(ops, lib_option, B, N, D,
         close("d_v", vt.grad, dv)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_softmax_attention_pool_wrappers_keep_their_entry_points(ops, monkeypatch, dtype):
+    """The two wrappers share one autograd Function and keep their own entry points: softmax_attention_pool launches
+    softmax_attention_pool_{fwd,bwd}[_bf16], softmax_attention_pool_drop the _drop_ ones (bench.py and profiles/ key on the
+    names), each under the shapes (B, N, D, G) and (B, N, D, G, d_v wanted).  At p = 0 both reach the same kernel: every
+    result and gradient of the two is the same, bit for bit."""
+    B, N, D, G = 2, 3, 8, 2
+    sfx = "_bf16" if dtype == torch.bfloat16 else ""
+    logits = 2.0 * seeded.seeded_array((B, N, G), 251)
+    v = seeded.seeded_array((B, N, D), 252)
+    gp, ga = g(seeded.seeded_array((B, G, D), 253)), g(seeded.seeded_array((B, N, G), 254))
+    seen, inner = [], ops._launch
+    monkeypatch.setattr(ops, "_launch", lambda name, shape, *a, **k: (seen.append((name, shape)), inner(name, shape, *a, **k))[1])
+    got = {}
+    for wrapper in ("plain", "drop"):
+        lt, vt = g(logits, True), g(v).to(dtype).requires_grad_()
+        res = ops.softmax_attention_pool(lt, vt) if wrapper == "plain" else ops.softmax_attention_pool_drop(lt, vt, 0.0, 0, False)
+        assert len(res) == 2
+        alpha, pooled = res
+        ((pooled * gp).sum() + (alpha * ga).sum()).backward()
+        got[wrapper] = (alpha.detach(), pooled.detach(), lt.grad, vt.grad)
+    torch.cuda.synchronize()
+    monkeypatch.setattr(ops, "_launch", inner)
+    assert seen == [("softmax_attention_pool_fwd" + sfx, (B, N, D, G)), ("softmax_attention_pool_bwd" + sfx, (B, N, D, G, True)),
+                    ("softmax_attention_pool_drop_fwd" + sfx, (B, N, D, G)), ("softmax_attention_pool_drop_bwd" + sfx, (B, N, D, G, True))], seen
+    for name, a, b in zip(("alpha", "pooled", "d_logits", "d_v"), got["plain"], got["drop"]):
+        assert a.dtype == b.dtype and torch.equal(a, b), name
+
+
 def test_softmax_attention_pool_large_logits(ops):
     """softmax must be max-shifted: logits around +/-80 would overflow a naive exp."""
     B, N, D, G = 2, 36, 64, 4

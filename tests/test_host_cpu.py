@@ -236,6 +236,21 @@ def test_grad_slots_are_keyed_by_the_flat_buffer():
         ops.set_grad_slots(p2, None)
 
 
+def test_workspace_rounds_the_librarys_byte_count_up():
+    """ops._workspace: float32 elements for the bytes a vqa_*_workspace_bytes query asks for -- never fewer bytes (the loss and
+    top-k wrappers once rounded down), the byte count handed on as the library gave it, and for 0 bytes an empty tensor, or None
+    where the caller passes a null pointer (column_sum)."""
+    seen = []
+    for nbytes, elements in ((0, 0), (1, 1), (4, 1), (5, 2)):
+        ws, got = ops._workspace(lambda *dims: (seen.append(dims), nbytes)[1], 7, 9, device="cpu")
+        assert got == nbytes and ws.dtype == torch.float32 and ws.device.type == "cpu"
+        assert ws.numel() == elements and ws.numel() * ws.element_size() >= nbytes
+    assert seen == [(7, 9)] * 4
+    assert ops._workspace(lambda: 0, device="cpu", none_if_empty=True) == (None, 0)
+    ws, got = ops._workspace(lambda: 5, device="cpu", none_if_empty=True)
+    assert got == 5 and ws.numel() == 2
+
+
 def test_bench_refuses_to_measure_fewer_gpus_than_asked():
     """`bench.py --gpus N` without a launcher starts its own ranks and must fail loudly when the node has fewer than N
     GPUs (here: one more than this host has, at least 2) instead of printing an n_gpus=1 line (missing #1)."""

@@ -134,6 +134,23 @@ class Phase:
         """source: a _Target (its reduced slabs) or a tensor [M,N] (S = 1: an elementwise job on existing data)."""
         (self.pre_jobs if pre else self.jobs).append(dict(kind=kind, source=source, out=out, ldo=int(ldo), out_off=out_off, **kw))
 
+    def linear_grad(self, w, b, g, ldg, x, ldx, rows, form=TN, g_off=0, x_off=0, M=None, grads=None, cols=None):
+        """The parameter gradients of one linear layer y = x W^T + b from the gradient g at y: a target for g^T x over the `rows`
+        batch rows (form TN, or TN_A4), whose product also writes g's column sums; d_w and d_b in the tensors _grad_like hands out
+        for w and b, summed from the target by two EPI_SUM jobs.  -> (d_w, d_b).
+        M: rows of the block when w and b are the first of several adjacent ranks; grads: (d_w, d_b) when the caller took them
+        already -- d_b None: no bias gradient from this product; cols = (first, count): only that column block of d_w (x is one
+        part of a concatenated input)."""
+        M = w.shape[0] if M is None else M
+        off, N = (0, w.shape[1]) if cols is None else cols
+        gw, gb = (ops._grad_like(w), ops._grad_like(b)) if grads is None else grads
+        t = self.target(M, N)
+        self.gemm(t, form, g, ldg, x, ldx, rows, a_off=g_off, b_off=x_off, colsum=gb is not None)
+        self.job(EPI_SUM, t, gw, w.shape[1], out_off=off)
+        if gb is not None:
+            self.job(EPI_SUM, t, gb, M, colsum=True)
+        return gw, gb
+
     @classmethod
     def engine(cls, name=None, rows=None):
         """The engine of the phase called `name` whose products have `rows` batch rows (None: a phase outside the table)."""
@@ -338,6 +355,16 @@ def _adjacent(params):
                for i, p in enumerate(params))
 
 
+def _rank_blocks(*lists):
+    """The R ranks of a fusion as row blocks (rows, first row, then the block's tensor of every list -- weights, biases, their
+    gradients): ONE block of all R*H rows, standing at rank 0's tensors, when the members of every list are _adjacent; else
+    R blocks of H rows."""
+    R, H = len(lists[0]), lists[0][0].shape[0]
+    if all(_adjacent(members) for members in lists):
+        return [(R * H, 0) + tuple(members[0] for members in lists)]
+    return [(H, r * H) + tuple(members[r] for members in lists) for r in range(R)]
+
+
 def _f32c(*tensors):
     for t in tensors:
         if t is None:
@@ -416,11 +443,7 @@ class QuestionProjections(torch.autograd.Function):
                 gated = torch.empty(B, A, device=dev, dtype=torch.float32)
                 ph.job(EPI_GRAD, d, gated, A, pre=True, gate=1, aux=low, aux_off=g * B * A, ld_aux=A, gate_scale=scale)
                 d = gated
-            t = ph.target(A, K)
-            ph.gemm(t, TN, d, A, qd, K, B, b_off=g * B * K if dropped_in else 0, colsum=True)
-            gw, gb = ops._grad_like(ws[g]), ops._grad_like(bs[g])
-            ph.job(EPI_SUM, t, gw, K)
-            ph.job(EPI_SUM, t, gb, A, colsum=True)
+            gw, gb = ph.linear_grad(ws[g], bs[g], d, A, qd, K, B, x_off=g * B * K if dropped_in else 0)
             grads_w.append(gw)
             grads_b.append(gb)
         ph.run()
@@ -459,15 +482,10 @@ class GatesAndRankFactors(torch.autograd.Function):
             idx += 2 * R
             H = ws[0].shape[0]
             h2 = torch.empty(B, R, H, device=dev, dtype=torch.float32)
-            if _adjacent(ws) and _adjacent(bs):
-                t = ph.target(B, R * H)
-                ph.gemm(t, NT, lows[g], A, ws[0], A, A)
-                ph.job(EPI_LINEAR, t, h2, R * H, bias=bs[0].as_strided((R * H,), (1,)))
-            else:
-                for r in range(R):
-                    t = ph.target(B, H)
-                    ph.gemm(t, NT, lows[g], A, ws[r], A, A)
-                    ph.job(EPI_LINEAR, t, h2, R * H, out_off=r * H, bias=bs[r])
+            for rows, first, w0, b0 in _rank_blocks(ws, bs):
+                t = ph.target(B, rows)
+                ph.gemm(t, NT, lows[g], A, w0, A, A)
+                ph.job(EPI_LINEAR, t, h2, R * H, out_off=first, bias=b0)
             outs.append(h2)
         ph.run()
         ng = len(gate_groups)
@@ -499,12 +517,7 @@ class GatesAndRankFactors(torch.autograd.Function):
             dg = torch.empty(B, D, device=dev, dtype=torch.float32)
             ph.job(EPI_GRAD, gy, dg, D, pre=True, gate=2, aux=ys[i], ld_aux=D)
             ph.gemm(d_low_t[g], NN, dg, D, W, A, D)
-            t = ph.target(D, A)
-            ph.gemm(t, TN, dg, D, lows[g], A, B, colsum=True)
-            gw, gb = ops._grad_like(W), ops._grad_like(b)
-            ph.job(EPI_SUM, t, gw, A)
-            ph.job(EPI_SUM, t, gb, D, colsum=True)
-            out_grads += [gw, gb]
+            out_grads += ph.linear_grad(W, b, dg, D, lows[g], A, B)
         for k, (g, R) in enumerate(fusions):
             ws, bs = params[idx:idx + R], params[idx + R:idx + 2 * R]
             idx += 2 * R
@@ -516,22 +529,10 @@ class GatesAndRankFactors(torch.autograd.Function):
             gh = gh.contiguous()           # [B,R,H]
             gws = [ops._grad_like(w) for w in ws]
             gbs = [ops._grad_like(b) for b in bs]
-            if _adjacent(ws):
-                ph.gemm(d_low_t[g], NN, gh, R * H, ws[0], A, R * H)
-            else:
-                for r in range(R):
-                    ph.gemm(d_low_t[g], NN, gh, R * H, ws[r], A, H, a_off=r * H)
-            if _adjacent(ws) and _adjacent(gws) and _adjacent(bs) and _adjacent(gbs):
-                t = ph.target(R * H, A)
-                ph.gemm(t, TN, gh, R * H, lows[g], A, B, colsum=True)
-                ph.job(EPI_SUM, t, gws[0], A)
-                ph.job(EPI_SUM, t, gbs[0], R * H, colsum=True)
-            else:
-                for r in range(R):
-                    t = ph.target(H, A)
-                    ph.gemm(t, TN, gh, R * H, lows[g], A, B, a_off=r * H, colsum=True)
-                    ph.job(EPI_SUM, t, gws[r], A)
-                    ph.job(EPI_SUM, t, gbs[r], H, colsum=True)
+            for rows, first, w0 in _rank_blocks(ws):
+                ph.gemm(d_low_t[g], NN, gh, R * H, w0, A, rows, a_off=first)
+            for rows, first, w0, gw0, b0, gb0 in _rank_blocks(ws, gws, bs, gbs):
+                ph.linear_grad(w0, b0, gh, R * H, lows[g], A, B, g_off=first, M=rows, grads=(gw0, gb0))
             out_grads += gws + gbs
         d_lows = []
         for g in range(G):
@@ -588,11 +589,7 @@ class GlimpseProjections(torch.autograd.Function):
                 t = ph.target(B, D)
                 ph.gemm(t, NN_A4 if odd else NN, d_pre, G * A, ws[g], D, A, a_off=g * A)
                 ph.job(EPI_GRAD, t, d_pooled, G * D, out_off=g * D)
-            t = ph.target(A, D)
-            ph.gemm(t, TN_A4 if odd else TN, d_pre, G * A, pooled, G * D, B, a_off=g * A, b_off=g * D, colsum=True)
-            gw, gb = ops._grad_like(ws[g]), ops._grad_like(bs[g])
-            ph.job(EPI_SUM, t, gw, D)
-            ph.job(EPI_SUM, t, gb, A, colsum=True)
+            gw, gb = ph.linear_grad(ws[g], bs[g], d_pre, G * A, pooled, G * D, B, form=TN_A4 if odd else TN, g_off=g * A, x_off=g * D)
             gws.append(gw)
             gbs.append(gb)
         ph.run()
@@ -621,26 +618,20 @@ class VectorFusion(torch.autograd.Function):
         x = torch.empty(B, H, device=dev, dtype=torch.float32)
         ph = Phase(dev, "vector_fusion_fwd")
         adj = _adjacent(ws) and _adjacent(bs)
-        if adj:
-            t = ph.target(B, R * H)
+        for rows, first, w0, b0 in _rank_blocks(ws, bs):
+            t = ph.target(B, rows)
             off = 0
             for xpart in xs:
                 k = xpart.shape[1]
-                ph.gemm(t, NT, xpart, k, ws[0], Ktot, k, b_off=off)
+                ph.gemm(t, NT, xpart, k, w0, Ktot, k, b_off=off)
                 off += k
-            ph.job(EPI_RANK_PRODUCT, t, h1, H, bias=bs[0].as_strided((R * H,), (1,)), R=R, aux=h2, ld_aux=R * H, out2=x,
-                   p_drop=p_out, seed=seed_out, drop_ld=H)
-        else:
-            # ranks not contiguous in memory (no flat parameter buffer): one linear job per rank, then the rank product as
-            # an elementwise job of its own
-            for r in range(R):
-                t = ph.target(B, H)
-                off = 0
-                for xpart in xs:
-                    k = xpart.shape[1]
-                    ph.gemm(t, NT, xpart, k, ws[r], Ktot, k, b_off=off)
-                    off += k
-                ph.job(EPI_LINEAR, t, h1, R * H, out_off=r * H, bias=bs[r])
+            if adj:
+                ph.job(EPI_RANK_PRODUCT, t, h1, H, bias=b0, R=R, aux=h2, ld_aux=R * H, out2=x,
+                       p_drop=p_out, seed=seed_out, drop_ld=H)
+            else:
+                # ranks not contiguous in memory (no flat parameter buffer): one linear job per rank, then the rank product as
+                # an elementwise job of its own
+                ph.job(EPI_LINEAR, t, h1, R * H, out_off=first, bias=b0)
         if p_out:
             _note_mask("fusion_out", B, H, p_out, seed_out)
         ph.run()
@@ -669,33 +660,20 @@ class VectorFusion(torch.autograd.Function):
         ph.job(EPI_RANK_PRODUCT_BWD, d_x, d_h1, R * H, pre=True, R=R, aux=h2, aux2=h1, ld_aux=R * H, out2=d_h2)
         gws = [ops._grad_like(w) for w in ws]
         gbs = [ops._grad_like(b) for b in bs]
-        adj = _adjacent(ws) and _adjacent(gws) and _adjacent(bs) and _adjacent(gbs)
+        blocks = _rank_blocks(ws, gws, bs, gbs)
         d_xs = []
         off = 0
         for i, xpart in enumerate(xs):
             k = xpart.shape[1]
             t = ph.target(B, k)
-            if adj:
-                ph.gemm(t, NN, d_h1, R * H, ws[0], Ktot, R * H, b_off=off)
-            else:
-                for r in range(R):
-                    ph.gemm(t, NN, d_h1, R * H, ws[r], Ktot, H, a_off=r * H, b_off=off)
+            for rows, first, w0, _, _, _ in blocks:
+                ph.gemm(t, NN, d_h1, R * H, w0, Ktot, rows, a_off=first, b_off=off)
             dx = torch.empty(B, k, device=dev, dtype=torch.float32)
             ph.job(EPI_GRAD, t, dx, k, gate=1, aux=xpart, ld_aux=k)             # relu gate of the glimpse phase's output
             d_xs.append(dx)
-            if adj:
-                tw = ph.target(R * H, k)
-                ph.gemm(tw, TN, d_h1, R * H, xpart, k, B, colsum=(i == 0))
-                ph.job(EPI_SUM, tw, gws[0], Ktot, out_off=off)
-                if i == 0:
-                    ph.job(EPI_SUM, tw, gbs[0], R * H, colsum=True)
-            else:
-                for r in range(R):
-                    tw = ph.target(H, k)
-                    ph.gemm(tw, TN, d_h1, R * H, xpart, k, B, a_off=r * H, colsum=(i == 0))
-                    ph.job(EPI_SUM, tw, gws[r], Ktot, out_off=off)
-                    if i == 0:
-                        ph.job(EPI_SUM, tw, gbs[r], H, colsum=True)
+            for rows, first, w0, gw0, b0, gb0 in blocks:      # (the bias gradient from the first part's product alone)
+                ph.linear_grad(w0, b0, d_h1, R * H, xpart, k, B, g_off=first, M=rows, grads=(gw0, gb0 if i == 0 else None),
+                               cols=(off, k))
             off += k
         ph.run()
         return (d_h2, None, None, None, *d_xs, *gws, *gbs)
@@ -735,10 +713,6 @@ class Classifier(torch.autograd.Function):
             ph.gemm(t, NN, d_logits, C, w, K, C)
             d_x = torch.empty(B, K, device=dev, dtype=torch.float32)
             ph.job(EPI_GRAD, t, d_x, K, p_drop=p_x, seed=seed_x, drop_ld=K)
-        tw = ph.target(C, K)
-        ph.gemm(tw, TN, d_logits, C, x, K, B, colsum=True)
-        gw, gb = ops._grad_like(w), ops._grad_like(b)
-        ph.job(EPI_SUM, tw, gw, K)
-        ph.job(EPI_SUM, tw, gb, C, colsum=True)
+        gw, gb = ph.linear_grad(w, b, d_logits, C, x, K, B)
         ph.run()
         return d_x, gw, gb, None, None

@@ -205,6 +205,22 @@ def _ptr_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
+def _workspace(query, *dims, device, none_if_empty=False):
+    """(scratch tensor, nbytes) for a launcher: nbytes = query(*dims), the library's own figure (a vqa_*_workspace_bytes entry
+    point), and a float32 tensor of ceil(nbytes / 4) elements -- never fewer bytes than asked.  none_if_empty: None instead of
+    an empty tensor for 0 bytes."""
+    nbytes = query(*dims)
+    if none_if_empty and not nbytes:
+        return None, nbytes
+    return torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32), nbytes
+
+
+def _entry(base, dtype):
+    """(the _launch name, the library function) of an op that has a bf16 twin: `base` for fp32 regions, `base`_bf16 for bf16."""
+    name = base + _sfx(dtype)
+    return name, getattr(_lib.lib(), "vqa_" + name)
+
+
 class PairwiseRelationReduce(torch.autograd.Function):
     """K1.  v2[b,j,:] = sum_i alpha[b,i,glimpse] * (v[b,i,:]*q1[b,:] + v[b,j,:]*q2[b,:]).
     Replaces config/CoR2.py:191-199 + :216."""
@@ -220,9 +236,8 @@ class PairwiseRelationReduce(torch.autograd.Function):
         G = alpha.shape[2]
         v2 = torch.empty_like(v)
         a_ptr = ctypes.c_void_p(alpha.data_ptr() + 4 * glimpse)
-        name = "pairwise_relation_reduce_fwd" + _sfx(v.dtype)
-        _launch(name, (B, N, D, int(mode)), getattr(_lib.lib(), "vqa_" + name),
-                _p(v), _p(q1), _p(q2), a_ptr, G, _p(v2), B, N, D, int(mode))
+        name, fn = _entry("pairwise_relation_reduce_fwd", v.dtype)
+        _launch(name, (B, N, D, int(mode)), fn, _p(v), _p(q1), _p(q2), a_ptr, G, _p(v2), B, N, D, int(mode))
         ctx.save_for_backward(v, q1, q2, alpha)
         ctx.glimpse = glimpse
         ctx.set_materialize_grads(False)
@@ -246,12 +261,21 @@ class PairwiseRelationReduce(torch.autograd.Function):
         d_q2 = torch.empty_like(q2)
         d_v = torch.empty_like(v) if ctx.needs_input_grad[0] else None
         a_ptr = ctypes.c_void_p(alpha.data_ptr() + 4 * ctx.glimpse)
-        name = "pairwise_relation_reduce_bwd" + _sfx(v.dtype)
-        _launch(name, (B, N, D, d_v is not None, g_b is not None), getattr(_lib.lib(), "vqa_" + name),
-                _p(v), _p(q1), _p(q2), a_ptr, G, _p(g), _p(g_b), _p(d_alpha), _p(d_q1), _p(d_q2), _p(d_v), B, N, D)
+        name, fn = _entry("pairwise_relation_reduce_bwd", v.dtype)
+        _launch(name, (B, N, D, d_v is not None, g_b is not None), fn, _p(v), _p(q1), _p(q2), a_ptr, G, _p(g), _p(g_b),
+                _p(d_alpha), _p(d_q1), _p(d_q2), _p(d_v), B, N, D)
         d_alpha_full = torch.zeros_like(alpha)
         d_alpha_full[:, :, ctx.glimpse] = d_alpha
         return d_v, d_q1, d_q2, d_alpha_full, None, None, None
+
+
+def _relation_apply_fwd(v, t, c2, out, p_drop, seed):
+    """The one launch of the closed-form relation step: out = keep * (t + c2 * v), for RelationApply and the unfused
+    RelationProjection."""
+    B, N, D = v.shape
+    sv, sp = _seed_args(seed)
+    name, fn = _entry("relation_apply_fwd", v.dtype)
+    _launch(name, (B, N, D, float(p_drop) > 0), fn, _p(v), _p(t), _p(c2), _p(out), float(p_drop), sv, sp, B, N, D)
 
 
 class RelationApply(torch.autograd.Function):
@@ -267,10 +291,7 @@ class RelationApply(torch.autograd.Function):
         if t.shape != (B, D) or c2.shape != (B, D):
             raise ValueError("relation_apply: t and c2 must be [B,D] = %s" % ((B, D),))
         out = torch.empty_like(v)
-        sv, sp = _seed_args(seed)
-        name = "relation_apply_fwd" + _sfx(v.dtype)
-        _launch(name, (B, N, D, float(p_drop) > 0), getattr(_lib.lib(), "vqa_" + name), _p(v), _p(t), _p(c2), _p(out),
-                float(p_drop), sv, sp, B, N, D)
+        _relation_apply_fwd(v, t, c2, out, p_drop, seed)
         ctx.save_for_backward(v, c2)
         ctx.cfg = (float(p_drop), seed)
         return out
@@ -285,9 +306,9 @@ class RelationApply(torch.autograd.Function):
         d_c2 = torch.empty(B, D, device=v.device, dtype=torch.float32)
         d_v = torch.empty_like(v) if ctx.needs_input_grad[0] else None
         sv, sp = _seed_args(seed)
-        name = "relation_apply_bwd" + _sfx(v.dtype)
-        _launch(name, (B, N, D, p_drop > 0, d_v is not None), getattr(_lib.lib(), "vqa_" + name), _p(v), _p(c2), _p(g),
-                _p(d_t), _p(d_c2), _p(d_v), p_drop, sv, sp, B, N, D)
+        name, fn = _entry("relation_apply_bwd", v.dtype)
+        _launch(name, (B, N, D, p_drop > 0, d_v is not None), fn, _p(v), _p(c2), _p(g), _p(d_t), _p(d_c2), _p(d_v),
+                p_drop, sv, sp, B, N, D)
         return d_v, d_t, d_c2, None, None
 
 
@@ -297,10 +318,14 @@ def relation_apply(v, t, c2, p_drop=0.0, seed=0):
 
 class SoftmaxAttentionPool(torch.autograd.Function):
     """K3.  alpha = softmax over regions of logits [B,N,G]; pooled[b,g,:] = sum_n alpha[b,n,g] v[b,n,:].
-    Replaces F.softmax(dim=1) (config/CoR2.py:83-87,:132) + putils.bmatmul (config/CoR2.py:142)."""
+    Replaces F.softmax(dim=1) (config/CoR2.py:83-87,:132) + putils.bmatmul (config/CoR2.py:142).
+    drop = (p_drop, seed, want_first): the `_drop` entry points -- K3 + the input dropout of MyATT's glimpse projections
+    (config/CoR2.py:143-147) + the undropped glimpse 0 for CoR2's relation step: (alpha, pooled_dropped [B,G,D], first [B,D] if
+    wanted).  Replaces the plain form followed by a dropout pass over [B,G,D] and, backward, the mask multiply, a clone of
+    the full gradient and the slice add.  drop = None: the plain entry points, (alpha, pooled)."""
 
     @staticmethod
-    def forward(ctx, logits, v):
+    def forward(ctx, logits, v, drop):
         logits, v = _prep("logits", logits), _prep("v", v, _REGION_DTYPES)
         B, N, G = logits.shape
         if v.dim() != 3 or v.shape[0] != B or v.shape[1] != N:
@@ -308,50 +333,16 @@ class SoftmaxAttentionPool(torch.autograd.Function):
         D = v.shape[2]
         alpha = torch.empty_like(logits)
         pooled = torch.empty(B, G, D, device=v.device, dtype=torch.float32)
-        name = "softmax_attention_pool_fwd" + _sfx(v.dtype)
-        _launch(name, (B, N, D, G), getattr(_lib.lib(), "vqa_" + name), _p(logits), _p(v), _p(alpha), _p(pooled), B, N, D, G)
+        first, extra = None, ()
+        if drop is not None:
+            p_drop, seed, want_first = drop
+            first = torch.empty(B, D, device=v.device, dtype=torch.float32) if want_first else None
+            extra = (_p(first), float(p_drop), *_seed_args(seed))
+            ctx.cfg = (float(p_drop), seed)
+        name, fn = _entry("softmax_attention_pool_drop_fwd" if drop is not None else "softmax_attention_pool_fwd", v.dtype)
+        _launch(name, (B, N, D, G), fn, _p(logits), _p(v), _p(alpha), _p(pooled), *extra, B, N, D, G)
         ctx.save_for_backward(alpha, v)
-        ctx.set_materialize_grads(False)
-        return alpha, pooled
-
-    @staticmethod
-    def backward(ctx, d_alpha, d_pooled):
-        alpha, v = ctx.saved_tensors
-        B, N, G = alpha.shape
-        D = v.shape[2]
-        if d_pooled is None:
-            d_pooled = torch.zeros(B, G, D, device=v.device, dtype=torch.float32)
-        d_pooled = _prep("grad_pooled", d_pooled)
-        d_alpha = _prep("grad_alpha", d_alpha) if d_alpha is not None else None
-        d_logits = torch.empty_like(alpha)
-        d_v = torch.empty_like(v) if ctx.needs_input_grad[1] else None
-        name = "softmax_attention_pool_bwd" + _sfx(v.dtype)
-        _launch(name, (B, N, D, G, d_v is not None), getattr(_lib.lib(), "vqa_" + name),
-                _p(alpha), _p(v), _p(d_pooled), _p(d_alpha), _p(d_logits), _p(d_v), B, N, D, G)
-        return d_logits, d_v
-
-
-class SoftmaxAttentionPoolDrop(torch.autograd.Function):
-    """K3 + the input dropout of MyATT's glimpse projections (config/CoR2.py:143-147) + the undropped glimpse 0 for CoR2's
-    relation step: (alpha, pooled_dropped [B,G,D], first [B,D] or None).  Replaces softmax_attention_pool followed by a
-    dropout pass over [B,G,D] and, backward, the mask multiply, a clone of the full gradient and the slice add."""
-
-    @staticmethod
-    def forward(ctx, logits, v, p_drop, seed, want_first):
-        logits, v = _prep("logits", logits), _prep("v", v, _REGION_DTYPES)
-        B, N, G = logits.shape
-        if v.dim() != 3 or v.shape[0] != B or v.shape[1] != N:
-            raise ValueError("v must be [B,N,D] matching logits [B,N,G]")
-        D = v.shape[2]
-        alpha = torch.empty_like(logits)
-        pooled = torch.empty(B, G, D, device=v.device, dtype=torch.float32)
-        first = torch.empty(B, D, device=v.device, dtype=torch.float32) if want_first else None
-        sv, sp = _seed_args(seed)
-        name = "softmax_attention_pool_drop_fwd" + _sfx(v.dtype)
-        _launch(name, (B, N, D, G), getattr(_lib.lib(), "vqa_" + name), _p(logits), _p(v), _p(alpha), _p(pooled), _p(first),
-                float(p_drop), sv, sp, B, N, D, G)
-        ctx.save_for_backward(alpha, v)
-        ctx.cfg = (float(p_drop), seed)
+        ctx.drop = drop is not None
         ctx.set_materialize_grads(False)
         if first is None:
             return alpha, pooled
@@ -360,25 +351,29 @@ class SoftmaxAttentionPoolDrop(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_alpha, d_pooled, d_first=None):
         alpha, v = ctx.saved_tensors
-        p_drop, seed = ctx.cfg
         B, N, G = alpha.shape
         D = v.shape[2]
         if d_pooled is None:
             d_pooled = torch.zeros(B, G, D, device=v.device, dtype=torch.float32)
         d_pooled = _prep("grad_pooled", d_pooled)
         d_alpha = _prep("grad_alpha", d_alpha) if d_alpha is not None else None
-        d_first = _prep("grad_first", d_first) if d_first is not None else None
         d_logits = torch.empty_like(alpha)
         d_v = torch.empty_like(v) if ctx.needs_input_grad[1] else None
-        sv, sp = _seed_args(seed)
-        name = "softmax_attention_pool_drop_bwd" + _sfx(v.dtype)
-        _launch(name, (B, N, D, G, d_v is not None), getattr(_lib.lib(), "vqa_" + name), _p(alpha), _p(v), _p(d_pooled),
-                _p(d_first), _p(d_alpha), _p(d_logits), _p(d_v), p_drop, sv, sp, B, N, D, G)
-        return d_logits, d_v, None, None, None
+        if ctx.drop:
+            p_drop, seed = ctx.cfg
+            d_first = _prep("grad_first", d_first) if d_first is not None else None
+            name, fn = _entry("softmax_attention_pool_drop_bwd", v.dtype)
+            _launch(name, (B, N, D, G, d_v is not None), fn, _p(alpha), _p(v), _p(d_pooled), _p(d_first), _p(d_alpha),
+                    _p(d_logits), _p(d_v), p_drop, *_seed_args(seed), B, N, D, G)
+        else:
+            name, fn = _entry("softmax_attention_pool_bwd", v.dtype)
+            _launch(name, (B, N, D, G, d_v is not None), fn, _p(alpha), _p(v), _p(d_pooled), _p(d_alpha), _p(d_logits),
+                    _p(d_v), B, N, D, G)
+        return d_logits, d_v, None
 
 
 def softmax_attention_pool_drop(logits, v, p_drop=0.0, seed=0, want_first=False):
-    return SoftmaxAttentionPoolDrop.apply(logits, v, p_drop, seed, want_first)
+    return SoftmaxAttentionPool.apply(logits, v, (p_drop, seed, want_first))
 
 
 class AttentionLogits(torch.autograd.Function):
@@ -396,9 +391,8 @@ class AttentionLogits(torch.autograd.Function):
                              % (tuple(w.shape), tuple(bias.shape), tuple(x.shape)))
         logits = torch.empty(*x.shape[:-1], G, device=x.device, dtype=torch.float32)
         sv, sp = _seed_args(seed)
-        name = "attention_logits_fwd" + _sfx(x.dtype)
-        _launch(name, (M, K, G, float(p_drop) > 0), getattr(_lib.lib(), "vqa_" + name), _p(x), ld, _p(w), _p(bias),
-                _p(logits), float(p_drop), sv, sp, M, K, G)
+        name, fn = _entry("attention_logits_fwd", x.dtype)
+        _launch(name, (M, K, G, float(p_drop) > 0), fn, _p(x), ld, _p(w), _p(bias), _p(logits), float(p_drop), sv, sp, M, K, G)
         ctx.save_for_backward(x, w)
         ctx.bias = bias
         ctx.cfg = (float(p_drop), seed, M, K, G, ld)
@@ -412,13 +406,11 @@ class AttentionLogits(torch.autograd.Function):
         d_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         d_w = _grad_like(w)
         d_b = _grad_like(ctx.bias)
-        L_ = _lib.lib()
-        ws_bytes = L_.vqa_attention_logits_bwd_workspace_bytes(M, K, G)
-        ws = torch.empty((ws_bytes + 3) // 4, device=x.device, dtype=torch.float32)
+        ws, ws_bytes = _workspace(_lib.lib().vqa_attention_logits_bwd_workspace_bytes, M, K, G, device=x.device)
         sv, sp = _seed_args(seed)
-        name = "attention_logits_bwd" + _sfx(x.dtype)
-        _launch(name, (M, K, G, p_drop > 0, d_x is not None), getattr(L_, "vqa_" + name), _p(x), ld, _p(w), _p(d_logits),
-                _p(d_x), _p(d_w), _p(d_b), _p(ws), ws_bytes, p_drop, sv, sp, M, K, G)
+        name, fn = _entry("attention_logits_bwd", x.dtype)
+        _launch(name, (M, K, G, p_drop > 0, d_x is not None), fn, _p(x), ld, _p(w), _p(d_logits), _p(d_x), _p(d_w), _p(d_b),
+                _p(ws), ws_bytes, p_drop, sv, sp, M, K, G)
         return d_x, d_w, d_b, None, None
 
 
@@ -437,6 +429,32 @@ _K4_FORM = os.environ.get("VQA_K4_FORM", "auto")
 _K4_FOLD_MIN_BATCH = 32
 
 
+def _fusion_operands(x, h2, params, x_dtype):
+    """The prelude of both K4 Functions: params = R weights then R biases -> (x, h2, w1, b1, (lead, B, N, R, H, L)), checked.
+    fp32: L is x's last dim; bf16: x's last dim is the weights' L zero-padded to a multiple of 64."""
+    R = len(params) // 2
+    w1 = [_prep("w1[%d]" % r, params[r]) for r in range(R)]
+    b1 = [_prep("b1[%d]" % r, params[R + r]) for r in range(R)]
+    x, h2 = _prep("x", x, (x_dtype,)), _prep("h2", h2)
+    lead = x.shape[:-1]
+    B, L = x.shape[0], x.shape[-1]
+    N = 1
+    for s in lead[1:]:
+        N *= s
+    H = w1[0].shape[0]
+    if x_dtype == torch.bfloat16:
+        Lp, L = L, w1[0].shape[1]
+        if Lp % BF16_PAD or Lp < L:
+            raise ValueError("bf16 fusion: x's last dim (%d) must be L=%d zero-padded to a multiple of %d" % (Lp, L, BF16_PAD))
+    if h2.shape != (B, R, H):
+        raise ValueError("h2 must be [B,R,H] = %s, got %s" % ((B, R, H), tuple(h2.shape)))
+    for r in range(R):
+        if w1[r].shape != (H, L) or b1[r].shape != (H,):
+            raise ValueError("rank %d: weight %s / bias %s do not match (H=%d, L=%d)"
+                             % (r, tuple(w1[r].shape), tuple(b1[r].shape), H, L))
+    return x, h2, w1, b1, (lead, B, N, R, H, L)
+
+
 class LowRankBilinearFusion(torch.autograd.Function):
     """K4.  out[b,n,:] = sum_r (x[b,n,:] W1_r^T + b1_r) * h2[b,r,:]   (x may also be [B,L]).
     Replaces the region side of putils.MutanFusion.forward (putils/__init__.py:232-238)."""
@@ -446,23 +464,7 @@ class LowRankBilinearFusion(torch.autograd.Function):
         # gate_dx: x is the relu output of the layer in front (compress_v / compress_v2); d_x comes back already multiplied
         # by (x > 0), that layer's own relu gradient (in the store of the data-gradient kernel where the folded form runs)
         ctx.gate_dx = bool(gate_dx)
-        R = len(params) // 2
-        w1 = [_prep("w1[%d]" % r, params[r]) for r in range(R)]
-        b1 = [_prep("b1[%d]" % r, params[R + r]) for r in range(R)]
-        x, h2 = _prep("x", x), _prep("h2", h2)
-        lead = x.shape[:-1]
-        B = x.shape[0]
-        L = x.shape[-1]
-        N = 1
-        for s in lead[1:]:
-            N *= s
-        H = w1[0].shape[0]
-        if h2.shape != (B, R, H):
-            raise ValueError("h2 must be [B,R,H] = %s, got %s" % ((B, R, H), tuple(h2.shape)))
-        for r in range(R):
-            if w1[r].shape != (H, L) or b1[r].shape != (H,):
-                raise ValueError("rank %d: weight %s / bias %s do not match (H=%d, L=%d)"
-                                 % (r, tuple(w1[r].shape), tuple(b1[r].shape), H, L))
+        x, h2, w1, b1, (lead, B, N, R, H, L) = _fusion_operands(x, h2, params, torch.float32)
         need_bwd = any(ctx.needs_input_grad)
         out = torch.empty(*lead, H, device=x.device, dtype=torch.float32)
         L_ = _lib.lib()
@@ -503,14 +505,12 @@ class LowRankBilinearFusion(torch.autograd.Function):
         d_w1 = [_grad_like(w) for w in w1]
         d_b1 = [_grad_like(b) for b in (b1 if ctx.folded else ctx.b1)]
         if ctx.folded:
-            ws_bytes = L_.vqa_lowrank_bilinear_fusion_folded_bwd_workspace_bytes(B, N, L, H, R)
-            ws = torch.empty((ws_bytes + 3) // 4, device=dev, dtype=torch.float32)
+            ws, ws_bytes = _workspace(L_.vqa_lowrank_bilinear_fusion_folded_bwd_workspace_bytes, B, N, L, H, R, device=dev)
             _launch("lowrank_bilinear_fusion_bwd", (B, N, L, H, R, d_x is not None), L_.vqa_lowrank_bilinear_fusion_folded_bwd_gated,
                     _p(x), L, _ptr_array(w1), _ptr_array(b1), _p(h2), _p(g), _p(d_x), _ptr_array(d_w1), _ptr_array(d_b1),
                     _p(d_h2), _p(ws), ws_bytes, B, N, L, H, R, int(ctx.gate_dx and d_x is not None))
             return (d_x, d_h2, None, *d_w1, *d_b1)
-        ws_bytes = L_.vqa_lowrank_bilinear_fusion_bwd_workspace_bytes(B, N, L, H, R)
-        ws = torch.empty((ws_bytes + 3) // 4, device=dev, dtype=torch.float32)
+        ws, ws_bytes = _workspace(L_.vqa_lowrank_bilinear_fusion_bwd_workspace_bytes, B, N, L, H, R, device=dev)
         _launch("lowrank_bilinear_fusion_bwd", (B, N, L, H, R, d_x is not None), L_.vqa_lowrank_bilinear_fusion_bwd,
                 _p(x), L, _ptr_array(w1), _p(h2), _p(h1), _p(g), _p(d_x), _ptr_array(d_w1), _ptr_array(d_b1), _p(d_h2),
                 _p(ws), ws_bytes, B, N, L, H, R)
@@ -672,8 +672,7 @@ def gemm_bf16_tn(a, b, outs=None, out_rows=None, out_cols=None, p_drop=0.0, seed
     if b.shape[0] != K:
         raise ValueError("gemm_bf16_tn: a [K,N1] and b [K,N2] must share K")
     L_ = _lib.lib()
-    ws_bytes = L_.vqa_gemm_bf16_tn_workspace_bytes(K, N1, N2)
-    ws = torch.empty((ws_bytes + 3) // 4, device=a.device, dtype=torch.float32)
+    ws, ws_bytes = _workspace(L_.vqa_gemm_bf16_tn_workspace_bytes, K, N1, N2, device=a.device)
     if outs is None and not p_drop:
         c = torch.empty(N1, N2, device=a.device, dtype=torch.float32)
         _launch("gemm_bf16_tn", (K, N1, N2), L_.vqa_gemm_bf16_tn, _p(a), N1, _p(b), N2, _p(c), _p(ws), ws_bytes, K, N1, N2)
@@ -774,25 +773,8 @@ class LowRankBilinearFusionBf16(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h2, gate_dx, packed, *params):
-        R = len(params) // 2
-        w1 = [_prep("w1[%d]" % r, params[r]) for r in range(R)]
-        b1 = [_prep("b1[%d]" % r, params[R + r]) for r in range(R)]
-        x, h2 = _prep("x", x, (torch.bfloat16,)), _prep("h2", h2)
-        lead = x.shape[:-1]
-        B, Lp = x.shape[0], x.shape[-1]
-        N = 1
-        for s in lead[1:]:
-            N *= s
-        H, L = w1[0].shape
-        Hp = pad_to(H, 256)
-        if Lp % BF16_PAD or Lp < L:
-            raise ValueError("bf16 fusion: x's last dim (%d) must be L=%d zero-padded to a multiple of %d" % (Lp, L, BF16_PAD))
-        if h2.shape != (B, R, H):
-            raise ValueError("h2 must be [B,R,H] = %s, got %s" % ((B, R, H), tuple(h2.shape)))
-        for r in range(R):
-            if w1[r].shape != (H, L) or b1[r].shape != (H,):
-                raise ValueError("rank %d: weight %s / bias %s do not match (H=%d, L=%d)"
-                                 % (r, tuple(w1[r].shape), tuple(b1[r].shape), H, L))
+        x, h2, w1, b1, (lead, B, N, R, H, L) = _fusion_operands(x, h2, params, torch.bfloat16)
+        Lp, Hp = x.shape[-1], pad_to(H, 256)
         dev = x.device
         if packed is not None:
             w1p, b1p, w1t = packed
@@ -847,14 +829,12 @@ class LowRankBilinearFusionBf16(torch.autograd.Function):
         L_ = _lib.lib()
         if ctx.fold is not None:
             w1p, b1p = ctx.fold
-            ws_bytes = L_.vqa_bilinear_fold_bwd_bf16_workspace_bytes(B, N, Lp, Hp, R)
-            ws = torch.empty((ws_bytes + 3) // 4, device=dev, dtype=torch.float32)
+            ws, ws_bytes = _workspace(L_.vqa_bilinear_fold_bwd_bf16_workspace_bytes, B, N, Lp, Hp, R, device=dev)
             _launch("lowrank_bilinear_fusion_bwd_bf16", (B, N, Lp, Hp, R, d_x is not None), L_.vqa_bilinear_fold_bwd_bf16,
                     _p(x), _p(w1p), _p(w1t), _p(b1p), _p(h2), _p(g), _p(d_x), _ptr_array(d_w1), _ptr_array(d_b1), _p(d_h2),
                     _p(ws), ws_bytes, B, N, Lp, Hp, R, H, L, int(gate_dx and d_x is not None))
             return (d_x, d_h2, None, None, *d_w1, *d_b1)
-        ws_bytes = L_.vqa_lowrank_bilinear_fusion_bwd_bf16_workspace_bytes(B, N, Lp, Hp, R)
-        ws = torch.empty((ws_bytes + 3) // 4, device=dev, dtype=torch.float32)
+        ws, ws_bytes = _workspace(L_.vqa_lowrank_bilinear_fusion_bwd_bf16_workspace_bytes, B, N, Lp, Hp, R, device=dev)
         args = (_p(x), _p(w1t), _p(h2), _p(h1), _p(g), _p(d_x), _ptr_array(d_w1), _ptr_array(d_b1), _p(d_h2), _p(ws), ws_bytes,
                 B, N, Lp, Hp, R, H, L, int(gate_dx and d_x is not None))
         _launch("lowrank_bilinear_fusion_bwd_bf16", (B, N, Lp, Hp, R, d_x is not None),
@@ -894,8 +874,7 @@ class ObjectDifferenceAttention(torch.autograd.Function):
         d_vl, d_ql, d_w = torch.empty_like(vl), torch.empty_like(ql), _grad_like(w)
         d_bias = _grad_like(ctx.bias)
         L_ = _lib.lib()
-        ws_bytes = L_.vqa_object_difference_attention_bwd_workspace_bytes(B, N, L, G)
-        ws = torch.empty((ws_bytes + 3) // 4, device=vl.device, dtype=torch.float32)
+        ws, ws_bytes = _workspace(L_.vqa_object_difference_attention_bwd_workspace_bytes, B, N, L, G, device=vl.device)
         sv, sp = _seed_args(seed)
         _launch("object_difference_attention_bwd", (B, N, L, G, p_drop > 0), L_.vqa_object_difference_attention_bwd,
                 _p(vl), _p(ql), _p(w), _p(d_logits), _p(d_vl), _p(d_ql), _p(d_w), _p(d_bias), _p(ws), ws_bytes,
@@ -933,8 +912,7 @@ def _linear_fwd(x, w, bias, y, M, K, N, act, p_drop, seed):
     L_ = _lib.lib()
     sv, sp = _seed_args(seed)
     if split_products(M, K, N, K, p_drop, tensors=(x, w)):
-        ws_bytes = L_.vqa_linear_act_fwd_split_workspace_bytes(K, N)
-        ws = torch.empty((ws_bytes + 3) // 4, device=x.device, dtype=torch.float32)
+        ws, ws_bytes = _workspace(L_.vqa_linear_act_fwd_split_workspace_bytes, K, N, device=x.device)
         _launch("linear_act_fwd_split", (M, K, N, float(p_drop) > 0), L_.vqa_linear_act_fwd_split, _p(x), K, _p(w), _p(bias),
                 _p(y), _p(ws), ws_bytes, M, K, N, int(act), float(p_drop), sv, sp)
     else:
@@ -948,15 +926,13 @@ def _linear_dw(x, w, y, gy, d_w, d_b, M, K, N, act, p_drop, seed, gz_out=None):
     L_ = _lib.lib()
     sv, sp = _seed_args(seed)
     if split_products(M, K, N, K, p_drop, weight_gradient=True, tensors=(x, d_w, gy, y if act == 1 else None)):
-        ws_bytes = L_.vqa_linear_act_dw_split_workspace_bytes(M, K, N)
-        ws = torch.empty((ws_bytes + 3) // 4, device=x.device, dtype=torch.float32)
+        ws, ws_bytes = _workspace(L_.vqa_linear_act_dw_split_workspace_bytes, M, K, N, device=x.device)
         _launch("linear_act_dw_split", (M, K, N, p_drop > 0, act), L_.vqa_linear_act_dw_split, _p(x), K,
                 _p(y) if act == 1 else None, _p(gy), _p(d_w), _p(d_b), _p(gz_out) if gz_out is not None else None, _p(ws), ws_bytes,
                 M, K, N, act, p_drop, sv, sp)
     else:
         assert gz_out is None
-        ws_bytes = L_.vqa_linear_act_bwd_workspace_bytes(M, K, N)
-        ws = torch.empty((ws_bytes + 3) // 4, device=x.device, dtype=torch.float32)
+        ws, ws_bytes = _workspace(L_.vqa_linear_act_bwd_workspace_bytes, M, K, N, device=x.device)
         _launch("linear_act_bwd", (M, K, N, p_drop > 0, False), L_.vqa_linear_act_bwd,
                 _p(x), K, _p(w), _p(y), _p(gy), None, _p(d_w), _p(d_b), _p(ws), ws_bytes, M, K, N, act, p_drop, sv, sp)
 
@@ -1010,8 +986,7 @@ class LinearAct(torch.autograd.Function):
             _linear_dw(x, w, y, gy, d_w, d_b, M, K, N, act, p_drop, seed)
             return d_x, d_w, d_b, None, None, None, None
         L_ = _lib.lib()
-        ws_bytes = L_.vqa_linear_act_bwd_workspace_bytes(M, K, N)
-        ws = torch.empty((ws_bytes + 3) // 4, device=x.device, dtype=torch.float32)
+        ws, ws_bytes = _workspace(L_.vqa_linear_act_bwd_workspace_bytes, M, K, N, device=x.device)
         sv, sp = _seed_args(seed)
         _launch("linear_act_bwd", (M, K, N, p_drop > 0, in_kernel_dx), L_.vqa_linear_act_bwd,
                 _p(x), K, _p(w), _p(y), _p(gy), _p(d_x), _p(d_w), _p(d_b), _p(ws), ws_bytes,
@@ -1056,8 +1031,7 @@ class RelationProjection(torch.autograd.Function):
         # (relation_mode 0), the fp32 MFMA engine and shapes outside the fused form.
         fused = pairwise is None and relation_linear_fused(v, t, c2, w, p_drop)
         if fused:
-            ws_bytes = L_.vqa_linear_act_fwd_split_workspace_bytes(D, L)
-            ws = torch.empty((ws_bytes + 3) // 4, device=v.device, dtype=torch.float32)
+            ws, ws_bytes = _workspace(L_.vqa_linear_act_fwd_split_workspace_bytes, D, L, device=v.device)
             _launch("relation_linear_fwd_split", (B, N, D, L, float(p_drop) > 0), L_.vqa_relation_linear_fwd_split, _p(v), _p(t), _p(c2),
                     _p(w), _p(bias), _p(y), _p(ws), ws_bytes, B, N, D, L, 1, float(p_drop), sv, sp)
             ctx.save_for_backward(v, t, c2, w, y)
@@ -1070,8 +1044,7 @@ class RelationProjection(torch.autograd.Function):
                 _launch("pairwise_relation_reduce_fwd", (B, N, D, 0), L_.vqa_pairwise_relation_reduce_drop_fwd, _p(v), _p(q1), _p(q2),
                         a_ptr, alpha.shape[2], _p(x), float(p_drop), sv, sp, B, N, D)
             else:
-                _launch("relation_apply_fwd", (B, N, D, float(p_drop) > 0), L_.vqa_relation_apply_fwd, _p(v), _p(t), _p(c2), _p(x),
-                        float(p_drop), sv, sp, B, N, D)
+                _relation_apply_fwd(v, t, c2, x, p_drop, seed)
             _linear_fwd(x, w, bias, y, M, D, L, 1, 0.0, 0)
             ctx.save_for_backward(v, x, w, y)
         ctx.fused = fused
@@ -1099,8 +1072,7 @@ class RelationProjection(torch.autograd.Function):
             # already multiplied by relu'(y) -- the packing pass then neither gates nor writes a copy
             sv, sp = _seed_args(seed)
             gz = gy if pregated else torch.empty_like(gy)
-            ws_bytes = L_.vqa_linear_act_dw_split_workspace_bytes(M, D, L)
-            ws = torch.empty((ws_bytes + 3) // 4, device=v.device, dtype=torch.float32)
+            ws, ws_bytes = _workspace(L_.vqa_linear_act_dw_split_workspace_bytes, M, D, L, device=v.device)
             _launch("relation_linear_dw_split", (M, D, L, p_drop > 0, 0 if pregated else 1), L_.vqa_relation_linear_dw_split, _p(v), _p(t),
                     _p(c2), None if pregated else _p(y), _p(gy), _p(d_w), _p(d_b), None if pregated else _p(gz), _p(ws), ws_bytes,
                     B, N, D, L, 0 if pregated else 1, p_drop, sv, sp)
@@ -1115,8 +1087,7 @@ class RelationProjection(torch.autograd.Function):
         sv, sp = _seed_args(seed)
         if (f32_products() == "split" and L_.vqa_relation_projection_dgrad_split_supported(B, N, D, L) == 1
                 and all(t.data_ptr() % 16 == 0 for t in (v, gz, w))):
-            ws_bytes = L_.vqa_relation_projection_dgrad_split_workspace_bytes(D, L)
-            ws = torch.empty((ws_bytes + 3) // 4, device=v.device, dtype=torch.float32)
+            ws, ws_bytes = _workspace(L_.vqa_relation_projection_dgrad_split_workspace_bytes, D, L, device=v.device)
             _launch("relation_projection_dgrad_split", (B, N, D, L, p_drop > 0), L_.vqa_relation_projection_dgrad_split, _p(gz), _p(w),
                     _p(v), _p(d_t), _p(d_c2), _p(ws), ws_bytes, p_drop, sv, sp, B, N, D, L)
         else:
@@ -1162,13 +1133,11 @@ def column_sum(x, out=None, cols=None):
     N = ld if cols is None else int(cols)
     if not 0 < N <= ld:
         raise ValueError("column_sum: cols=%r outside (0, %d]" % (cols, ld))
-    L_ = _lib.lib()
-    ws_bytes = L_.vqa_column_sum_workspace_bytes(M, N)
-    ws = torch.empty((ws_bytes + 3) // 4, device=x.device, dtype=torch.float32) if ws_bytes else None
+    ws, ws_bytes = _workspace(_lib.lib().vqa_column_sum_workspace_bytes, M, N, device=x.device, none_if_empty=True)
     if out is None or out.dtype != torch.float32 or out.shape != (N,) or not out.is_contiguous():
         out = torch.empty(N, device=x.device, dtype=torch.float32)
-    name = "column_sum" + _sfx(x.dtype)
-    _launch(name, (M, N), getattr(L_, "vqa_" + name), _p(x), ld, _p(out), _p(ws), ws_bytes, M, N)
+    name, fn = _entry("column_sum", x.dtype)
+    _launch(name, (M, N), fn, _p(x), ld, _p(out), _p(ws), ws_bytes, M, N)
     return out
 
 
@@ -1226,8 +1195,7 @@ class LinearFn(torch.autograd.Function):
             d_w = _grad_like(w)
             d_b = _grad_like(ctx.bias) if ctx.has_bias else None
             L_ = _lib.lib()
-            ws_bytes = L_.vqa_linear_act_bwd_workspace_bytes(M, K, N)
-            ws = torch.empty((ws_bytes + 3) // 4, device=x.device, dtype=torch.float32)
+            ws, ws_bytes = _workspace(L_.vqa_linear_act_bwd_workspace_bytes, M, K, N, device=x.device)
             _launch("linear_act_bwd", (M, K, N, False, False), L_.vqa_linear_act_bwd, _p(x2), K, _p(w), _p(y2), _p(gy2),
                     None, _p(d_w), _p(d_b), _p(ws), ws_bytes, M, K, N, 1 if mask_in_kernel else 0, 0.0, 0, None)
             return d_x, d_w, d_b, None
@@ -1243,7 +1211,7 @@ class LinearFn(torch.autograd.Function):
             d_b = column_sum(gy2, out=_grad_like(ctx.bias) if ctx.bias.dtype == torch.float32 else None).to(gy.dtype)
         return d_x, d_w, d_b, None
 
-    engine_dw = __import__("os").environ.get("VQA_ENGINE_DW", "1") == "1"
+    engine_dw = os.environ.get("VQA_ENGINE_DW", "1") == "1"
 
 
 class StackParams(torch.autograd.Function):
@@ -1613,8 +1581,7 @@ def gemm_tn_split(g, g_off, ldg, x, x_off, ldx, d_w, M, N1, N2):
     if (L_.vqa_gemm_tn_split_supported(M, N1, N2, int(ldg), int(ldx)) != 1 or gp % 8 or xp % 16 or d_w.data_ptr() % 16
             or not d_w.is_contiguous()):
         return False
-    nbytes = L_.vqa_gemm_tn_split_workspace_bytes(M, N1, N2)
-    ws = torch.empty((nbytes + 3) // 4, device=d_w.device, dtype=torch.float32)
+    ws, nbytes = _workspace(L_.vqa_gemm_tn_split_workspace_bytes, M, N1, N2, device=d_w.device)
     _launch("gemm_tn_split", (M, N1, N2), L_.vqa_gemm_tn_split, ctypes.c_void_p(gp), int(ldg), ctypes.c_void_p(xp), int(ldx), _p(d_w), _p(ws),
             nbytes, M, N1, N2)
     return True
@@ -1633,6 +1600,105 @@ def _grouped_products(name, problems, engine=None):
     ph.run()
 
 
+def _gru_forward(ctx, gi, w, masks, af, bf16):
+    """forward of GruSequence (bf16 False) and GruSequenceBf16 (True): one loop; the two differ in the history's dtype and row
+    length, in how W is prepared once per pass, in the step product and in the gate entry point (which takes the row length)."""
+    from . import head
+    gi, w = _prep("gi", gi), _prep("w", w)
+    masks = _prep("masks", masks) if masks is not None else None
+    G, B, T, H = gi.shape
+    if G != 3 or w.shape != (3, H, H) or (masks is not None and masks.shape != (3, B, H)):
+        raise ValueError("gru_sequence: gi [3,B,T,H], w [3,H,H], masks [3,B,H] expected")
+    if bf16 and H % 8:
+        raise ValueError("gru_sequence: compute_dtype=bfloat16 needs a hidden size that is a multiple of 8, got H = %d" % H)
+    code = {"relu": 1, "tanh": 3}[af]
+    dev = gi.device
+    Hp = pad_to(H) if bf16 else H                                          # bf16: rows padded to a multiple of 64, pads never written
+    out = torch.empty(T, B, H, device=dev, dtype=torch.float32)
+    hist = torch.zeros(3, T, B, Hp, device=dev, dtype=torch.bfloat16 if bf16 else torch.float32)   # hm_t = h_{t-1} * m_g; hm_0 = 0
+    saved = torch.empty(4, T, B, H, device=dev, dtype=torch.float32)       # r, i, n, a_n
+    h0 = torch.zeros(B, H, device=dev, dtype=torch.float32)
+    a = torch.empty(3, B, H, device=dev, dtype=torch.float32)
+    gs = T * B * Hp
+    fast = None
+    if bf16:
+        wb = pack_bf16(w, torch.zeros(3, H, Hp, device=dev, dtype=torch.bfloat16), H * Hp, Hp, 1, zero_fill=False)
+    else:
+        fast = gemm_nt_split_batched_ok(B, H, H, H, hist, w)
+        img = split_weights(w) if fast else None
+    name, fn = _entry("gru_gates_fwd", hist.dtype)
+    row = (Hp,) if bf16 else ()
+    for t in range(T):
+        if t == 0:
+            a.zero_()                                                        # hm_0 = 0: no product to form
+        elif bf16:
+            gru_gemm_bf16(hist, t * B * Hp, gs, Hp, wb, H * Hp, Hp, a, 3, B, H, H)                      # a[g] = hm_t[g] Wb_g^T
+        elif fast:
+            gemm_nt_split_batched(hist, t * B * H, gs, H, img, a, None, w, False, 3, B, H, H)          # a[g] = hm_t[g] W_g^T
+        else:
+            _grouped_products("gru_step_fwd", [(head.NT, hist, g * gs + t * B * H, H, w, g * H * H, H, B, H, H, a[g]) for g in range(3)])
+        nxt = ctypes.c_void_p(hist.data_ptr() + hist.element_size() * (t + 1) * B * Hp) if t + 1 < T else None
+        _launch(name, (B, T, H), fn, _p(gi), _p(a), _p(out[t - 1] if t else h0), _p(masks), _p(out[t]), nxt, gs, *row,
+                _p(saved[0, t]), _p(saved[1, t]), _p(saved[2, t]), _p(saved[3, t]), B, T, H, t, code)
+    ctx.save_for_backward(w, masks, out, hist, saved, h0)
+    ctx.cfg = (B, T, H, Hp, code, fast)
+    return out
+
+
+def _gru_backward(ctx, d_out, bf16):
+    """backward of both GRU Functions: the gate gradients step by step, the data-gradient product against W^T (prepared once),
+    then the recurrent weight gradient over all T*B rows of the two histories."""
+    from . import head
+    w, masks, out, hist, saved, h0 = ctx.saved_tensors
+    B, T, H, Hp, code, fast = ctx.cfg
+    d_out = _prep("grad_out", d_out)
+    dev = d_out.device
+    L_ = _lib.lib()
+    if bf16:
+        gz = torch.zeros(3, T, B, Hp, device=dev, dtype=torch.bfloat16)        # gzb_t = bf(gz_t)
+    else:
+        gz = torch.empty(3, T, B, H, device=dev, dtype=torch.float32)
+    d_gi = torch.empty(3, B, T, H, device=dev, dtype=torch.float32)
+    carry = [torch.empty(B, H, device=dev, dtype=torch.float32) for _ in range(2)]
+    gs = T * B * Hp
+    buf = torch.empty(3, B, H, device=dev, dtype=torch.float32)
+    if bf16:
+        wbt = pack_bf16(w, torch.zeros(3, H, Hp, device=dev, dtype=torch.bfloat16), H * Hp, 1, Hp, zero_fill=False)   # Wb_g^T
+    else:
+        img_t = split_weights(w, transposed=True) if fast else None
+    name, fn = _entry("gru_gates_bwd", hist.dtype)
+    row = (Hp,) if bf16 else ()
+    dhm = None
+    for t in range(T - 1, -1, -1):
+        _launch(name, (B, T, H), fn, _p(d_out[t]), _p(carry[(t + 1) & 1]) if t + 1 < T else None, _p(dhm), _p(masks),
+                _p(saved[0, t]), _p(saved[1, t]), _p(saved[2, t]), _p(saved[3, t]), _p(out[t - 1] if t else h0),
+                ctypes.c_void_p(gz.data_ptr() + gz.element_size() * t * B * Hp), gs, *row, _p(d_gi), _p(carry[t & 1]), B, T, H, t, code)
+        if t == 0:
+            break
+        if bf16:                                                            # gradient at hm_t: dhm[g] = gz_t[g] W_g   [3,B,H]
+            dhm = gru_gemm_bf16(gz, t * B * Hp, gs, Hp, wbt, H * Hp, Hp, buf, 3, B, H, H)
+        elif fast:
+            dhm = gemm_nt_split_batched(gz, t * B * H, gs, H, img_t, buf, None, w, True, 3, B, H, H)
+        else:
+            _grouped_products("gru_step_bwd", [(head.NN, gz, g * gs + t * B * H, H, w, g * H * H, H, B, H, H, buf[g]) for g in range(3)])
+            dhm = buf
+    d_w = None
+    if ctx.needs_input_grad[1]:
+        # d_w[g] = gz[g]^T hm[g] over all T*B rows, written straight into the gradient's slot
+        d_w = _grad_like(w)
+        if bf16:
+            ws, ws_bytes = _workspace(L_.vqa_gemm_bf16_tn_workspace_bytes, T * B, H, H, device=dev)
+            for g in range(3):
+                _launch("gemm_bf16_tn", (T * B, H, H), L_.vqa_gemm_bf16_tn, ctypes.c_void_p(gz.data_ptr() + 2 * g * gs), Hp,
+                        ctypes.c_void_p(hist.data_ptr() + 2 * g * gs), Hp, _p(d_w[g]), _p(ws), ws_bytes, T * B, H, H)
+        else:
+            rest = [g for g in range(3) if not (fast and gemm_tn_split(gz, g * gs, H, hist, g * gs, H, d_w[g], T * B, H, H))]
+            if rest:      # (short sequences / odd widths: the grouped launch, contraction split into slabs and summed in fixed order)
+                _grouped_products("gru_dw", [(head.TN, gz, g * gs, H, hist, g * gs, H, H, H, T * B, d_w[g]) for g in rest],
+                                  engine="split" if (f32_products() == "split" and T * B >= 384) else None)
+    return d_gi, d_w, None, None
+
+
 class GruSequence(torch.autograd.Function):
     """The recurrent part of putils.BayesianGRU.forward (putils/__init__.py:704-731): T steps of
     r,i = sigmoid(gi_{r,i}[t] + W_h{r,i}(h*m)), n = af(gi_n[t] + r * W_hn(h*m_n)), h = (1-i) n + i h.
@@ -1646,72 +1712,11 @@ class GruSequence(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, gi, w, masks, af):
-        gi, w = _prep("gi", gi), _prep("w", w)
-        masks = _prep("masks", masks) if masks is not None else None
-        G, B, T, H = gi.shape
-        if G != 3 or w.shape != (3, H, H) or (masks is not None and masks.shape != (3, B, H)):
-            raise ValueError("gru_sequence: gi [3,B,T,H], w [3,H,H], masks [3,B,H] expected")
-        code = {"relu": 1, "tanh": 3}[af]
-        dev = gi.device
-        L_ = _lib.lib()
-        out = torch.empty(T, B, H, device=dev, dtype=torch.float32)
-        hist = torch.zeros(3, T, B, H, device=dev, dtype=torch.float32)        # hm_t = h_{t-1} * m_g; hm_0 = 0
-        saved = torch.empty(4, T, B, H, device=dev, dtype=torch.float32)       # r, i, n, a_n
-        h0 = torch.zeros(B, H, device=dev, dtype=torch.float32)
-        a = torch.empty(3, B, H, device=dev, dtype=torch.float32)
-        gs = T * B * H
-        fast = gemm_nt_split_batched_ok(B, H, H, H, hist, w)
-        img = split_weights(w) if fast else None
-        for t in range(T):
-            if t == 0:
-                a.zero_()                                                        # hm_0 = 0: no product to form
-            elif fast:
-                gemm_nt_split_batched(hist, t * B * H, gs, H, img, a, None, w, False, 3, B, H, H)          # a[g] = hm_t[g] W_g^T
-            else:
-                from . import head
-                _grouped_products("gru_step_fwd", [(head.NT, hist, g * gs + t * B * H, H, w, g * H * H, H, B, H, H, a[g]) for g in range(3)])
-            nxt = ctypes.c_void_p(hist.data_ptr() + 4 * (t + 1) * B * H) if t + 1 < T else None
-            _launch("gru_gates_fwd", (B, T, H), L_.vqa_gru_gates_fwd, _p(gi), _p(a), _p(out[t - 1] if t else h0), _p(masks),
-                    _p(out[t]), nxt, gs, _p(saved[0, t]), _p(saved[1, t]), _p(saved[2, t]), _p(saved[3, t]), B, T, H, t, code)
-        ctx.save_for_backward(w, masks, out, hist, saved, h0)
-        ctx.cfg = (B, T, H, code, fast)
-        return out
+        return _gru_forward(ctx, gi, w, masks, af, False)
 
     @staticmethod
     def backward(ctx, d_out):
-        from . import head
-        w, masks, out, hist, saved, h0 = ctx.saved_tensors
-        B, T, H, code, fast = ctx.cfg
-        d_out = _prep("grad_out", d_out)
-        dev = d_out.device
-        L_ = _lib.lib()
-        gz = torch.empty(3, T, B, H, device=dev, dtype=torch.float32)
-        d_gi = torch.empty(3, B, T, H, device=dev, dtype=torch.float32)
-        carry = [torch.empty(B, H, device=dev, dtype=torch.float32) for _ in range(2)]
-        gs = T * B * H
-        buf = torch.empty(3, B, H, device=dev, dtype=torch.float32)
-        img_t = split_weights(w, transposed=True) if fast else None
-        dhm = None
-        for t in range(T - 1, -1, -1):
-            _launch("gru_gates_bwd", (B, T, H), L_.vqa_gru_gates_bwd, _p(d_out[t]), _p(carry[(t + 1) & 1]) if t + 1 < T else None,
-                    _p(dhm), _p(masks), _p(saved[0, t]), _p(saved[1, t]), _p(saved[2, t]), _p(saved[3, t]),
-                    _p(out[t - 1] if t else h0), ctypes.c_void_p(gz.data_ptr() + 4 * t * B * H), gs, _p(d_gi), _p(carry[t & 1]),
-                    B, T, H, t, code)
-            if t > 0:                                                           # gradient at hm_t: dhm[g] = gz_t[g] W_g   [3,B,H]
-                if fast:
-                    dhm = gemm_nt_split_batched(gz, t * B * H, gs, H, img_t, buf, None, w, True, 3, B, H, H)
-                else:
-                    _grouped_products("gru_step_bwd", [(head.NN, gz, g * gs + t * B * H, H, w, g * H * H, H, B, H, H, buf[g]) for g in range(3)])
-                    dhm = buf
-        d_w = None
-        if ctx.needs_input_grad[1]:
-            # d_w[g] = gz[g]^T hm[g] over all T*B rows: one grouped launch, contraction split into slabs and summed in fixed order
-            d_w = _grad_like(w)
-            rest = [g for g in range(3) if not (fast and gemm_tn_split(gz, g * gs, H, hist, g * gs, H, d_w[g], T * B, H, H))]
-            if rest:      # (short sequences / odd widths: the grouped launch, contraction split into slabs and summed in fixed order)
-                _grouped_products("gru_dw", [(head.TN, gz, g * gs, H, hist, g * gs, H, H, H, T * B, d_w[g]) for g in rest],
-                                  engine="split" if (f32_products() == "split" and T * B >= 384) else None)
-        return d_gi, d_w, None, None
+        return _gru_backward(ctx, d_out, False)
 
 
 def gru_gemm_bf16(a, a_off, a_gs, lda, w, w_gs, ldw, c, G, M, N, K):
@@ -1729,71 +1734,15 @@ class GruSequenceBf16(torch.autograd.Function):
     histories of the GEMM operands hm_t = bf(h_{t-1} * m_g) and gzb_t = bf(gz_t) with rows padded to a multiple of 64 (zero pads,
     never written), fp32 accumulation, fp32 state / gates / saved tensors / d_gi.  Per step one vqa_gru_gemm_bf16 and one
     vqa_gru_gates_*_bf16 launch each way; the recurrent weight gradient is three vqa_gemm_bf16_tn launches (fixed-order slabs)
-    over the two histories at the end.  Same loop structure as GruSequence; any B >= 1, H % 8 == 0."""
+    over the two histories at the end.  Any B >= 1, H % 8 == 0."""
 
     @staticmethod
     def forward(ctx, gi, w, masks, af):
-        gi, w = _prep("gi", gi), _prep("w", w)
-        masks = _prep("masks", masks) if masks is not None else None
-        G, B, T, H = gi.shape
-        if G != 3 or w.shape != (3, H, H) or (masks is not None and masks.shape != (3, B, H)):
-            raise ValueError("gru_sequence: gi [3,B,T,H], w [3,H,H], masks [3,B,H] expected")
-        if H % 8:
-            raise ValueError("gru_sequence: compute_dtype=bfloat16 needs a hidden size that is a multiple of 8, got H = %d" % H)
-        code = {"relu": 1, "tanh": 3}[af]
-        dev = gi.device
-        L_ = _lib.lib()
-        Hp = pad_to(H)
-        out = torch.empty(T, B, H, device=dev, dtype=torch.float32)
-        hist = torch.zeros(3, T, B, Hp, device=dev, dtype=torch.bfloat16)      # hm_t = bf(h_{t-1} * m_g); hm_0 = 0
-        saved = torch.empty(4, T, B, H, device=dev, dtype=torch.float32)       # r, i, n, a_n
-        h0 = torch.zeros(B, H, device=dev, dtype=torch.float32)
-        a = torch.empty(3, B, H, device=dev, dtype=torch.float32)
-        gs = T * B * Hp
-        wb = pack_bf16(w, torch.zeros(3, H, Hp, device=dev, dtype=torch.bfloat16), H * Hp, Hp, 1, zero_fill=False)
-        for t in range(T):
-            if t == 0:
-                a.zero_()                                                        # hm_0 = 0: no product to form
-            else:
-                gru_gemm_bf16(hist, t * B * Hp, gs, Hp, wb, H * Hp, Hp, a, 3, B, H, H)                      # a[g] = hm_t[g] Wb_g^T
-            nxt = ctypes.c_void_p(hist.data_ptr() + 2 * (t + 1) * B * Hp) if t + 1 < T else None
-            _launch("gru_gates_fwd_bf16", (B, T, H), L_.vqa_gru_gates_fwd_bf16, _p(gi), _p(a), _p(out[t - 1] if t else h0), _p(masks),
-                    _p(out[t]), nxt, gs, Hp, _p(saved[0, t]), _p(saved[1, t]), _p(saved[2, t]), _p(saved[3, t]), B, T, H, t, code)
-        ctx.save_for_backward(w, masks, out, hist, saved, h0)
-        ctx.cfg = (B, T, H, Hp, code)
-        return out
+        return _gru_forward(ctx, gi, w, masks, af, True)
 
     @staticmethod
     def backward(ctx, d_out):
-        w, masks, out, hist, saved, h0 = ctx.saved_tensors
-        B, T, H, Hp, code = ctx.cfg
-        d_out = _prep("grad_out", d_out)
-        dev = d_out.device
-        L_ = _lib.lib()
-        gz = torch.zeros(3, T, B, Hp, device=dev, dtype=torch.bfloat16)        # gzb_t = bf(gz_t)
-        d_gi = torch.empty(3, B, T, H, device=dev, dtype=torch.float32)
-        carry = [torch.empty(B, H, device=dev, dtype=torch.float32) for _ in range(2)]
-        gs = T * B * Hp
-        buf = torch.empty(3, B, H, device=dev, dtype=torch.float32)
-        wbt = pack_bf16(w, torch.zeros(3, H, Hp, device=dev, dtype=torch.bfloat16), H * Hp, 1, Hp, zero_fill=False)   # Wb_g^T
-        dhm = None
-        for t in range(T - 1, -1, -1):
-            _launch("gru_gates_bwd_bf16", (B, T, H), L_.vqa_gru_gates_bwd_bf16, _p(d_out[t]),
-                    _p(carry[(t + 1) & 1]) if t + 1 < T else None, _p(dhm), _p(masks), _p(saved[0, t]), _p(saved[1, t]),
-                    _p(saved[2, t]), _p(saved[3, t]), _p(out[t - 1] if t else h0), ctypes.c_void_p(gz.data_ptr() + 2 * t * B * Hp), gs,
-                    Hp, _p(d_gi), _p(carry[t & 1]), B, T, H, t, code)
-            if t > 0:                                                           # gradient at hm_t: dhm[g] = gzb_t[g] Wb_g   [3,B,H]
-                dhm = gru_gemm_bf16(gz, t * B * Hp, gs, Hp, wbt, H * Hp, Hp, buf, 3, B, H, H)
-        d_w = None
-        if ctx.needs_input_grad[1]:
-            # d_w[g] = gzb[g]^T hm[g] over all T*B rows, written straight into the gradient's slot
-            d_w = _grad_like(w)
-            ws_bytes = L_.vqa_gemm_bf16_tn_workspace_bytes(T * B, H, H)
-            ws = torch.empty((ws_bytes + 3) // 4, device=dev, dtype=torch.float32)
-            for g in range(3):
-                _launch("gemm_bf16_tn", (T * B, H, H), L_.vqa_gemm_bf16_tn, ctypes.c_void_p(gz.data_ptr() + 2 * g * gs), Hp,
-                        ctypes.c_void_p(hist.data_ptr() + 2 * g * gs), Hp, _p(d_w[g]), _p(ws), ws_bytes, T * B, H, H)
-        return d_gi, d_w, None, None
+        return _gru_backward(ctx, d_out, True)
 
 
 def parse_compute_dtype(value, name="compute_dtype"):
@@ -1903,8 +1852,7 @@ class EncoderInputBf16(torch.autograd.Function):
         if ctx.needs_input_grad[3]:
             # d_w[g] = dgb_g^T xb_g over all M rows, the padded columns cropped: straight into the master-shaped gradient
             d_w = _grad_like(w_in)
-            ws_bytes = L_.vqa_gemm_bf16_tn_workspace_bytes(M, H, Kp)
-            ws = torch.empty((ws_bytes + 3) // 4, device=dev, dtype=torch.float32)
+            ws, ws_bytes = _workspace(L_.vqa_gemm_bf16_tn_workspace_bytes, M, H, Kp, device=dev)
             for g in range(3):
                 _launch("gemm_bf16_tn", (M, H, Kp), L_.vqa_gemm_bf16_tn_ex, ctypes.c_void_p(dgb.data_ptr() + 2 * g * M * Hp), Hp,
                         ctypes.c_void_p(xb.data_ptr() + 2 * (g if planes == 3 else 0) * M * Kp), Kp, _ptr_array([d_w[g]]), 1, H, H,
@@ -1993,17 +1941,16 @@ def _loss_and_grad(kind, logits, target, scale, kmax, want_grad=True):
     lib = _lib.lib()
     family = "vqa_mean_loss" if mean else "vqa_kld_sum_loss"
     hits, shape = None, (B, C, want_grad)
-    if kmax is None:
-        nbytes = getattr(lib, family + "_workspace_bytes")(B)
-    else:
+    query, dims = getattr(lib, family + "_workspace_bytes"), (B,)
+    if kmax is not None:
         kmax, name = int(kmax), name + "_hits"
         _check_k(name, C, kmax)
         hits, shape = torch.empty(kmax, device=lg.device, dtype=torch.int32), (B, C, kmax)
-        nbytes = getattr(lib, family + "_hits_workspace_bytes")(B, kmax)
+        query, dims = getattr(lib, family + "_hits_workspace_bytes"), (B, kmax)
         args = [_p(hits), kmax] + args
     loss = torch.empty((), device=lg.device, dtype=torch.float32)
     d_logits = torch.empty_like(lg) if want_grad else None
-    ws = torch.empty(nbytes // 4, device=lg.device, dtype=torch.float32)
+    ws, nbytes = _workspace(query, *dims, device=lg.device)
     _launch(name, shape, getattr(lib, "vqa_" + name), _p(lg), _p(target), _p(loss), _p(d_logits), *args, _p(ws), nbytes, B, C)
     return loss, d_logits, hits
 
@@ -2162,10 +2109,9 @@ def sparse_loss_and_grad(kind, logits, a_idx, a_val, scale=None, kmax=None, seed
         _check_k(name, C, kmax)
         hits, shape = torch.empty(kmax, device=lg.device, dtype=torch.int32), (B, C, K, kmax)
         args = [_p(hits), kmax] + args
-    nbytes = lib.vqa_sparse_loss_workspace_bytes(B, kmax or 0)
     loss = torch.empty((), device=lg.device, dtype=torch.float32)
     d_logits = torch.empty_like(lg)
-    ws = torch.empty(nbytes // 4, device=lg.device, dtype=torch.float32)
+    ws, nbytes = _workspace(lib.vqa_sparse_loss_workspace_bytes, B, kmax or 0, device=lg.device)
     head = [_p(lg), _p(a_idx), _p(a_val)] + ([_p(labels)] if kind == "CE" else [])
     _launch(name, shape, getattr(lib, "vqa_" + name), *head, _p(loss), _p(d_logits), *args, _p(ws), nbytes, B, C, K)
     return (loss, d_logits, hits) if kind != "CE" else (loss, d_logits, hits, labels)
@@ -2223,8 +2169,7 @@ def predict_topk(logits, k, target=None, probs=True):
         if target.shape != lg.shape:
             raise ValueError("predict_topk: target must be [B,C] like the logits, got %s" % (tuple(target.shape),))
         hits = torch.empty(k, device=lg.device, dtype=torch.int32)
-        nbytes = _lib.lib().vqa_predict_topk_workspace_bytes(B, k)
-        ws = torch.empty(nbytes // 4, device=lg.device, dtype=torch.int32)
+        ws, nbytes = _workspace(_lib.lib().vqa_predict_topk_workspace_bytes, B, k, device=lg.device)
     _launch("predict_topk", (B, C, k), _lib.lib().vqa_predict_topk, _p(lg), _p(target), _p(top_idx), _p(top_prob), _p(hits), k,
             _p(ws), nbytes, B, C)
     return top_idx, top_prob, hits
@@ -2402,7 +2347,7 @@ def pairwise_relation_reduce(v, q1, q2, alpha, glimpse=0, mode=1, dual=False):
 
 
 def softmax_attention_pool(logits, v):
-    return SoftmaxAttentionPool.apply(logits, v)
+    return SoftmaxAttentionPool.apply(logits, v, None)
 
 
 def lowrank_bilinear_fusion(x, h2, weights, biases, gate_dx=False, packed=None):
