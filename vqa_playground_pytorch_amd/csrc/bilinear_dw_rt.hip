@@ -97,6 +97,7 @@ __global__ __launch_bounds__(rt::kThreads, 1) void bilinear_dw_rt_kernel(DwRtArg
   // the ones column: element L (even) of a row sits in the last span, lane (L % 64) / 4, component L % 4 -- local
   // component 0 of the half (L % 4) / 2; its neighbour L + 1 is forced to 0
   const bool one_lane = (r == (L % 64) / 4) && (eh == (L % 4) / 2);
+  const bool past_row = 64 * (kSpans - 1) + 4 * r + 2 * eh > L;   // the lane's column pair of the last span lies past L + 1
 
   f32x4 acc[R][kSpans][2];   // folded dW (+ db in column L): [rank][span][local component] over the 4 rows t
 #pragma unroll
@@ -220,7 +221,10 @@ __global__ __launch_bounds__(rt::kThreads, 1) void bilinear_dw_rt_kernel(DwRtArg
             wq[rk][t] = *reinterpret_cast<const f32x2*>(Ws + (rk * 16 + 4 * gq + t) * kCols + 64 * q + 4 * r + 2 * eh);
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-          const f32x4 pv = P[q][e];
+          f32x4 pv = P[q][e];
+          // the lane's columns past L + 1 were multiplied with what lies behind the row in memory, the NEXT row of x: nothing of
+          // them is stored and W is zero there, but a NaN of the next sample's first row would reach this sample's dh2 as 0 * NaN
+          if (q == kSpans - 1) pv = past_row ? f32x4{0.f, 0.f, 0.f, 0.f} : pv;
 #pragma unroll
           for (int rk = 0; rk < R; ++rk) {
             acc[rk][q][e] += h2v[rk] * pv;

@@ -563,7 +563,8 @@ static TileChoice dw_tile() { return tile_override_or({64, 64, 2}); }
 // per-sample form: worth it when a sample fills most of its padded stages and the ranks fit in registers
 static bool dw_per_sample(int N, int R) {
   const int padded = (N + 15) / 16 * 16;
-  if (const char* e = vqa::option("VQA_K4_DW_FORM")) return std::atoi(e) != 0 && R <= 4;  // experiment knob
+  // experiment knob (the per-sample kernel is instantiated for ranks 2..4 only: rank 1 keeps the scaled form whatever it says)
+  if (const char* e = vqa::option("VQA_K4_DW_FORM")) return std::atoi(e) != 0 && R >= 2 && R <= 4;
   return R >= 2 && R <= 4 && N * 4 >= padded * 3;
 }
 static long dw_max_samples_per_slab(int R) { return 65536 / ((long)R * 64 * (long)sizeof(float)); }
@@ -730,10 +731,8 @@ extern "C" int vqa_lowrank_bilinear_fusion_bwd(const float* x, int ldx, const fl
 // sample form, 133 us + 8 us reduce (sweeps: 19 slabs of the 16-row form 137 + 12; 32 slabs 141 + 19).  The kernel is
 // bound by the L2 -> LDS operand traffic of its 64x64 tiles (16 FLOP per byte), not by barriers or padding.
 static int dw_fold_bk(int N, int R) {
-  static const int knob = [] {   // experiment knob: 16 forces the three-stage form at 32 < N <= 40
-    const char* e = vqa::option("VQA_K4_FOLD_DW_BK");
-    return e != nullptr ? std::atoi(e) : 0;
-  }();
+  const char* e = vqa::option("VQA_K4_FOLD_DW_BK");   // experiment knob: 16 forces the three-stage form at 32 < N <= 40
+  const int knob = e != nullptr ? std::atoi(e) : 0;
   return (N > 32 && N <= 40 && R <= 2 && knob != 16) ? 40 : 16;
 }
 static int dw_fold_splits(int B, int N, int H, int L, int R) {
@@ -752,8 +751,12 @@ static int dw_fold_splits(int B, int N, int H, int L, int R) {
 static size_t folded_bwd_floats(int B, int N, int L, int H, int R, size_t* wt_off, size_t* slab_off, size_t* db_off,
                                 size_t* part_off) {
   int S = dw_fold_splits(B, N, H, L, R);
-  if (dw_split_supported(B, N, L, H, R, L) && S < kDwSplitSlabs) S = kDwSplitSlabs;      // (the split form's slab count)
   const int tiles_n = (L + 63) / 64;
+  int parts = 2 * tiles_n;   // dh2 partial sums: two per column tile of the LDS-tile kernel (the register-tile form writes two)
+  if (dw_split_supported(B, N, L, H, R, L)) {
+    if (S < kDwSplitSlabs) S = kDwSplitSlabs;   // (the split form's slab count)
+    if (parts < 4) parts = 4;                   // (and its four column quarters, whatever L: L <= 64 has one column tile)
+  }
   size_t off = 0;
   *wt_off = off;
   off += (size_t)R * L * H;
@@ -763,7 +766,7 @@ static size_t folded_bwd_floats(int B, int N, int L, int H, int R, size_t* wt_of
   off += (size_t)S * R * H;
   off = (off + 3) / 4 * 4;
   *part_off = off;
-  off += (size_t)2 * tiles_n * B * R * H;
+  off += (size_t)parts * B * R * H;
   return off;
 }
 
@@ -815,17 +818,18 @@ extern "C" int vqa_lowrank_bilinear_fusion_folded_bwd_gated(const float* x, int 
 
   // (1) dx = Weff^T g on the folded kernel (needs W1_r^T, contraction-contiguous)
   if (d_x != nullptr) {
+    // (refused before the transpose goes out: a refusal launches nothing)
+    VQA_REQUIRE(!gate_dx || ldx == L, VQA_E_UNSUPPORTED, "lowrank_bilinear_fusion_folded_bwd: gate_dx needs a dense x (ldx == L)");
     rc = folded_transpose_weights(w1, wt, L, H, R, s);
     if (rc != VQA_OK) return rc;
     const float* wtp[kFoldMaxR];
     for (int r = 0; r < R; ++r) wtp[r] = wt + (size_t)r * L * H;
-    VQA_REQUIRE(!gate_dx || ldx == L, VQA_E_UNSUPPORTED, "lowrank_bilinear_fusion_folded_bwd: gate_dx needs a dense x (ldx == L)");
     rc = folded_data_gradient(g, wtp, h2, d_x, B, N, L, H, R, s, gate_dx ? x : nullptr);
     if (rc != VQA_OK) return rc;
   }
   // (2) P_b = g_b^T x_b once per sample: dW1_r, db1_r slabs and dh2
   if (dw_split_supported(B, N, L, H, R, ldx)) {
-    // split engine (bilinear_dw_split.hip): 16 slabs, dh2 in four partial sums (the workspace holds 2 * tiles_n >= 4 of them)
+    // split engine (bilinear_dw_split.hip): 16 slabs, dh2 in four partial sums (folded_bwd_floats leaves room for four)
     rc = dw_split_launch(g, x, h2, w1, b1, slab, dbslab, part, B, N, L, H, R, s);
     if (rc != VQA_OK) return rc;
     const int HL2 = H * L;
@@ -848,10 +852,8 @@ extern "C" int vqa_lowrank_bilinear_fusion_folded_bwd_gated(const float* x, int 
   }
   const int S = dw_fold_splits(B, N, H, L, R);
   const int tiles_m = (H + 63) / 64, tiles_n = (L + 63) / 64;
-  static const int pf = [] {   // register sets in flight (experiment knob; 1 keeps three waves per SIMD at R = 2)
-    const char* e = vqa::option("VQA_K4_FOLD_DW_PF");
-    return e != nullptr && std::atoi(e) == 2 ? 2 : 1;
-  }();
+  const char* pf_opt = vqa::option("VQA_K4_FOLD_DW_PF");   // register sets in flight (experiment knob; 1 keeps three waves per SIMD at R = 2)
+  const int pf = pf_opt != nullptr && std::atoi(pf_opt) == 2 ? 2 : 1;
   const int bk = dw_fold_bk(N, R);
   const int spl = (B + S - 1) / S, SP = (N + bk - 1) / bk;
   const uint32_t inv = (uint32_t)((1ull << 32) / (uint32_t)(SP * bk)) + 1u;
