@@ -4,7 +4,10 @@ datasets.py:405-412) into the `.npy` file feed.FeatureStore memory-maps.  Needs 
 wherever the dataset was extracted).  For a contiguous (un-chunked) dataset it also prints the byte offset of the array
 inside the .hy file: FeatureStore(path_to_hy, names, shape=..., offset=...) then reads the original file in place.
 
-    python tools/hy_to_npy.py /data/VQA/preprocess/size,rcnn_arch,224.hy /data/VQA/preprocess/size,rcnn_arch,224.npy"""
+    python tools/hy_to_npy.py /data/VQA/preprocess/size,rcnn_arch,224.hy /data/VQA/preprocess/size,rcnn_arch,224.npy
+
+--counts NAME DST.npy (adaptive features, zero-padded to a fixed number of rows): also copy the integer dataset NAME [n_img] -- the
+number of real regions of every image -- into DST.npy, the file FeatureStore(counts=...) takes."""
 import sys
 
 import numpy as np
@@ -15,7 +18,11 @@ def main():
         import h5py
     except ImportError:
         sys.exit("hy_to_npy.py needs h5py (pip install h5py) -- it is a one-off conversion on the machine that holds the dataset")
-    src, dst = sys.argv[1:3]
+    args, counts = sys.argv[1:], None
+    if "--counts" in args:
+        i = args.index("--counts")
+        counts, args = args[i + 1:i + 3], args[:i] + args[i + 3:]
+    src, dst = args[:2]
     with h5py.File(src, "r") as hy:
         att = hy["att"]
         offset = att.id.get_offset()          # None for chunked / compressed layouts
@@ -25,6 +32,12 @@ def main():
         for lo in range(0, att.shape[0], step):
             out[lo:lo + step] = att[lo:lo + step]
         out.flush()
+        if counts is not None:
+            c = np.asarray(hy[counts[0]]).astype(np.int32).reshape(-1)
+            if c.shape[0] != att.shape[0] or c.min() < 1 or c.max() > att.shape[1]:
+                sys.exit("%s: expected %d region counts in 1..%d" % (counts[0], att.shape[0], att.shape[1]))
+            np.save(counts[1], c)
+            print("wrote", counts[1])
     print("wrote", dst)
 
 

@@ -115,6 +115,15 @@ SIGNATURES = {
                                                  _c_i, _c_i, _c_st]),
     "vqa_softmax_attention_pool_fwd_bf16": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_st]),
     "vqa_softmax_attention_pool_bwd_bf16": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_st]),
+    # K3 with a region count per sample (lens: device int32 [B])
+    "vqa_softmax_attention_pool_len_fwd": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_fl, _c_u64, _c_f, _c_i, _c_i, _c_i, _c_i,
+                                                  _c_st]),
+    "vqa_softmax_attention_pool_len_bwd": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_fl, _c_u64, _c_f, _c_i, _c_i,
+                                                  _c_i, _c_i, _c_st]),
+    "vqa_softmax_attention_pool_len_fwd_bf16": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_fl, _c_u64, _c_f, _c_i, _c_i, _c_i,
+                                                       _c_i, _c_st]),
+    "vqa_softmax_attention_pool_len_bwd_bf16": (_c_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_fl, _c_u64, _c_f, _c_i,
+                                                       _c_i, _c_i, _c_i, _c_st]),
     "vqa_pack_bf16": (_c_i, [_c_f, _c_i, _c_i, _c_i, _c_f, _c_l, _c_l, _c_l, _c_sz, _c_i, _c_st]),
     "vqa_gemm_bf16_nt": (_c_i, [_c_f, _c_i, _c_f, _c_i, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_st]),
     "vqa_pack_many": (_c_i, [_c_f, _c_i, _c_sz, _c_st]),

@@ -186,6 +186,14 @@ class Model(nn.Module):
         v = sample["v"]
         b = v.size(0)
         v_feature = v.contiguous().view(b, -1, 2048)
+        # 'v_len' (optional): the number of real regions of every sample, the rest of its N rows being (finite) padding.
+        # Both attentions mask their softmax with it (K3 `_len_` kernels): alpha is exactly 0 on the padding, so the padded
+        # rows reach neither the pooled features, nor the relation step (alpha1[..., 0]), nor any gradient.
+        v_len = sample.get("v_len")
+        if v_len is not None:
+            if v_len.dim() != 1 or v_len.size(0) != b:
+                raise ValueError("v_len must be [B] = [%d], got %s" % (b, tuple(v_len.shape)))
+            v_len = ops.region_counts(v_len, v_feature.size(1), v_feature.device)
         if v_feature.dtype != self.compute_dtype:
             # bf16 regions into the fp32 path: the feed's transport format (feed.store_batches(region_dtype=torch.bfloat16): half
             # the host -> device bytes), widened exactly by one HIP pass; everything downstream is the fp32 step
@@ -206,7 +214,7 @@ class Model(nn.Module):
         fuse1 = self.fusion_vq1(v_feature_low, q_feature_low, relu_input=self.compress_v.grad_pregated,
                                 packed=shad.get("fusion_vq1"), h2=h2_1)
         v1_att, alpha1, alpha1_full, pooled1_first = self.att1.attend(v_feature, self.att1.conv_att.pre_activation(fuse1),
-                                                                return_pooled=True, grouped=grouped)
+                                                                return_pooled=True, grouped=grouped, lens=v_len)
         if _cut is not None:
             # everything the second reasoning step (relation, compress_v2, fusion_vq2, att2, fusion_final, classifier)
             # reads from the first.  The second step runs on detached aliases of these tensors, so a backward pass from the
@@ -254,7 +262,7 @@ class Model(nn.Module):
             v2_att, alpha2, _ = self.att2.attend(v_feature, self.att2.conv_att.pre_activation(fuse2),
                                                  lambda pooled, pd: ops.relation_apply(
                                                      pooled, t_b, c2_b, pd, ops.next_dropout_seed() if pd else 0),
-                                                 grouped=grouped)
+                                                 grouped=grouped, lens=v_len)
             # the reference's v2_feature[:, [0, 1], :] (visu.py:198-207 reads it after an eval forward).  Eval: computed here,
             # like the reference does.  Training: a step never looks at it, so it is computed when read, from copies of the
             # two region rows and of t / c2 rows that belong to THIS forward only when it ran eagerly -- under graph replay
@@ -274,7 +282,8 @@ class Model(nn.Module):
             v2_feature_low = self.compress_v2(v2_feature, packed=shad.get("compress_v2"))
             fuse2 = self.fusion_vq2(v2_feature_low, q_feature_low, relu_input=self.compress_v2.grad_pregated,
                                     packed=shad.get("fusion_vq2"), h2=h2_2)
-            v2_att, alpha2, _ = self.att2.attend(v2_for_pooling, self.att2.conv_att.pre_activation(fuse2), grouped=grouped)
+            v2_att, alpha2, _ = self.att2.attend(v2_for_pooling, self.att2.conv_att.pre_activation(fuse2), grouped=grouped,
+                                                 lens=v_len)
             feature = v2_feature[:, 0:2, :].detach().float()
 
         # side output read by visu.py:198-207; detached so it does not pin the autograd graph of the step

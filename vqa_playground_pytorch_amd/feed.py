@@ -50,8 +50,15 @@ def _pair_width(most):
     return max(1, int(most))
 
 
+def _check_count(count, regions, what):
+    if not 1 <= count <= regions:
+        raise ValueError("%s: region count %d outside 1..%d" % (what, count, regions))
+    return count
+
+
 def collate(items, num_ans, pin=False, answers="dense"):
-    """List of reference-style items {'v' [36,2048], 'q_idxes' [T], 'q_id', 'a_10_idx' or 'a', optionally 'a_mc_idx'} -> one batch dict of
+    """List of reference-style items {'v' [36,2048], 'q_idxes' [T], 'q_id', 'a_10_idx' or 'a', optionally 'a_mc_idx', optionally
+    'v_len' = the number of real (not padding) rows of 'v'} -> one batch dict of
     contiguous host tensors (optionally pinned), the layout Model.forward and the trainer expect.  answers="sparse": instead of the
     dense 'a' [B,num_ans] the pairs of 'a_10_idx' as they are, in record order -- 'a_idx' int32 [B,K] and 'a_val' float32 [B,K], K the
     batch's largest pair count, shorter rows padded with -1 / 0 (ops.densify defines the format; the trainer takes the two keys)."""
@@ -86,6 +93,11 @@ def collate(items, num_ans, pin=False, answers="dense"):
             if mc.numel() > MC_CANDIDATES:
                 raise ValueError("item %d has %d multiple-choice candidates, more than %d" % (i, mc.numel(), MC_CANDIDATES))
             batch["a_mc_idx"][i, :mc.numel()] = mc
+    if "v_len" in items[0]:
+        # per-item region counts (adaptive features padded to the store's N): int32 [B], what cor2.Model reads as sample['v_len']
+        batch["v_len"] = mk(B, dtype=torch.int32)
+        for i, it in enumerate(items):
+            batch["v_len"][i] = _check_count(int(it["v_len"]), v0.shape[0], "item %d" % i)
     for i, it in enumerate(items):
         batch["v"][i].copy_(torch.as_tensor(it["v"], dtype=torch.float32))
         batch["q_idxes"][i].copy_(torch.as_tensor(it["q_idxes"], dtype=torch.long))
@@ -199,9 +211,10 @@ class FeatureStore:
     names; `name_to_idx` is the reference's dict of the same name.  gather(indices, out) copies rows into `out` (a pinned host
     tensor [B,N,D] fp32, or bf16 -- then the rows are rounded on the way, half the PCIe bytes for the bf16 path) with `workers`
     threads; nothing is read until a row is asked for (the file stays on disk / in the page cache, like the reference's
-    h5py handle with load_mem=None, datasets.py:565-566)."""
+    h5py handle with load_mem=None, datasets.py:565-566).  counts: the images' region counts (1..N each, ValueError otherwise) for a
+    store of zero-padded adaptive features; store_batches then serves them as 'v_len'."""
 
-    def __init__(self, path, names=None, shape=None, offset=0, workers=4):
+    def __init__(self, path, names=None, shape=None, offset=0, workers=4, counts=None):
         if shape is None:
             self.features = np.load(path, mmap_mode="r")
         else:
@@ -216,6 +229,18 @@ class FeatureStore:
         self.name_to_idx = {n: i for i, n in enumerate(self.idx_to_name)} if names is not None else None
         if self.idx_to_name is not None and len(self.idx_to_name) != self.features.shape[0]:
             raise ValueError("feature store %s: %d names for %d feature rows" % (path, len(self.idx_to_name), self.features.shape[0]))
+        # counts (optional): a `.npy` path or an array of [n_img] integers, the number of real regions of every image (adaptive
+        # bottom-up features: 10..100 boxes).  The rows beyond an image's count are handed out as the file holds them, so the
+        # store must be ZERO-PADDED there (the models only ask for finite values; zeros are the contract).
+        self.counts = None
+        if counts is not None:
+            c = np.load(counts) if isinstance(counts, (str, os.PathLike)) else np.asarray(counts)
+            if c.ndim != 1 or c.shape[0] != self.features.shape[0] or not np.issubdtype(c.dtype, np.integer):
+                raise ValueError("feature store %s: counts must be %d integers, got %s %s" % (path, self.features.shape[0], c.dtype, c.shape))
+            if c.size and (c.min() < 1 or c.max() > self.features.shape[1]):
+                raise ValueError("feature store %s: region counts %d..%d outside 1..%d"
+                                 % (path, int(c.min()), int(c.max()), self.features.shape[1]))
+            self.counts = c.astype(np.int32)
         self.workers = max(1, int(workers))
         self._pool = ThreadPoolExecutor(self.workers) if self.workers > 1 else None
         self._lock = threading.Lock()
@@ -384,7 +409,8 @@ def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, p
     milliseconds: a generator per epoch would pay that again every time).  answers="sparse": instead of 'a' the batches carry the pairs
     as they are, 'a_idx' int32 [B,K] and 'a_val' float32 [B,K] in the same staging ring (K = the table's largest pair count, at most
     16; shorter rows padded with -1 / 0, pairs in record order): no dense [B,num_ans] row is allocated, filled or copied, the
-    trainer computes its loss from the pairs (ops.densify defines the format).  Records given with a dense 'a' cannot be served sparse."""
+    trainer computes its loss from the pairs (ops.densify defines the format).  Records given with a dense 'a' cannot be served sparse.
+    A store with region counts (FeatureStore(counts=...)) adds 'v_len' int32 [B] to every batch, from the same staging ring."""
     sparse = _check_answers(answers)
     n = len(qa_items.rows) if isinstance(qa_items, _QaTable) else len(qa_items)
 
@@ -411,10 +437,14 @@ def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, p
                 slots.append({"v": mk(batch_size, *store.sample_shape, dtype=region_dtype), "q_idxes": mk(batch_size, T, dtype=q_dtype),
                               "a": mk(batch_size, num_ans, dtype=torch.float32) if has_a and not sparse else None,
                               "a_idx": mk(batch_size, K, dtype=torch.int32) if K else None,
-                              "a_val": mk(batch_size, K, dtype=torch.float32) if K else None})
+                              "a_val": mk(batch_size, K, dtype=torch.float32) if K else None,
+                              "v_len": mk(batch_size, dtype=torch.int32) if store.counts is not None else None})
         s = slots[k]
         batch = {"v": store.gather(table.rows[ids], s["v"]), "q_idxes": s["q_idxes"][:b], "q_id": torch.from_numpy(table.q_ids[ids])}
         batch["q_idxes"].numpy()[...] = table.q[ids]
+        if store.counts is not None:
+            batch["v_len"] = s["v_len"][:b]
+            batch["v_len"].numpy()[...] = store.counts[table.rows[ids]]
         if K:
             batch["a_idx"], batch["a_val"] = s["a_idx"][:b], s["a_val"][:b]
             table.fill_pairs(batch["a_idx"], batch["a_val"], ids)

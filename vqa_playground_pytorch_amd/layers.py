@@ -384,23 +384,25 @@ class MyATT(nn.Module):
         return inputs.is_cuda and self.af == "relu" and self.inputs_dim % 2 == 0 and \
             all(getattr(m, "af", None) == "relu" and m.out_features == mods[0].out_features and m.p == mods[0].p for m in mods)
 
-    def attend(self, inputs, logits, pooled_map=None, return_pooled=False, grouped=False):
+    def attend(self, inputs, logits, pooled_map=None, return_pooled=False, grouped=False, lens=None):
         """logits [B,N,G] (pre-softmax) -> (x_v, list_att, alpha [B,N,G][, pooled[:, 0] [B,D]]).  pooled_map (optional):
         ``pooled_map(pooled, p) -> tensor`` transforms the pooled features before the glimpse projections AND applies
-        their input dropout at rate p (so the two share one pass).  (Nothing that carries an autograd graph is kept on
+        their input dropout at rate p (so the two share one pass).  lens (optional): int32 [B] on the inputs' device, the
+        number of real regions of every sample -- the rows beyond get alpha = 0 exactly and are never read.  (Nothing that carries an autograd graph is kept on
         the module: a tensor stashed across steps would pin the previous step's graph.)"""
         first = None
         pd = self.glimpse_dropout()
+        counts = {} if lens is None else {"lens": lens}       # (without counts: today's calls, argument for argument)
         if pooled_map is None and inputs.is_cuda and (pd > 0 or return_pooled) and self._fused_dropout_ok():
             # the glimpse projections' input dropout rides in the pooling kernel's store (one pass fewer each way), and
             # glimpse 0 comes back undropped as its own tensor for the caller (CoR2's relation step)
-            res = ops.softmax_attention_pool_drop(logits, inputs, pd, ops.next_dropout_seed() if pd else 0, return_pooled)
+            res = ops.softmax_attention_pool_drop(logits, inputs, pd, ops.next_dropout_seed() if pd else 0, return_pooled, **counts)
             alpha, pooled = res[0], res[1]
             x_v = self.glimpse_projection(pooled, predropped=True, grouped=grouped)
             if return_pooled:
                 return x_v, torch.split(alpha, 1, dim=2), alpha, res[2]
             return x_v, torch.split(alpha, 1, dim=2), alpha
-        alpha, pooled = ops.softmax_attention_pool(logits, inputs)                     # [B,N,G], [B,G,D]
+        alpha, pooled = ops.softmax_attention_pool(logits, inputs, **counts)           # [B,N,G], [B,G,D]
         if return_pooled:       # glimpse 0 for the caller (CoR2's relation step), the whole tensor for the projections
             pooled, first = ops.with_first_group(pooled)
         if pooled_map is None:
@@ -411,8 +413,8 @@ class MyATT(nn.Module):
             return x_v, torch.split(alpha, 1, dim=2), alpha, first
         return x_v, torch.split(alpha, 1, dim=2), alpha
 
-    def forward(self, inputs, fuse):
-        x_v, list_att, _ = self.attend(inputs, self.conv_att.pre_activation(fuse))
+    def forward(self, inputs, fuse, lens=None):
+        x_v, list_att, _ = self.attend(inputs, self.conv_att.pre_activation(fuse), lens=lens)
         return x_v, list_att
 
 

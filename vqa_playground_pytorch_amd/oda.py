@@ -81,6 +81,10 @@ class Model(nn.Module):
         return logits, cut[0], cut[1]
 
     def forward(self, sample, _cut=None):
+        if "v_len" in sample:
+            # the attention weights of this model are indexed by region slot (fuse_dim = regions * 310): masking them is
+            # the object-difference kernel's business, which takes no counts
+            raise ValueError("ODA.Model takes no per-sample region counts: drop 'v_len' from the sample (CoR2Model masks with it)")
         v = sample["v"]
         b = v.size(0)
         v_feature = v.contiguous().view(b, -1, 2048)

@@ -325,7 +325,7 @@ class SoftmaxAttentionPool(torch.autograd.Function):
     the full gradient and the slice add.  drop = None: the plain entry points, (alpha, pooled)."""
 
     @staticmethod
-    def forward(ctx, logits, v, drop):
+    def forward(ctx, logits, v, drop, lens=None):
         logits, v = _prep("logits", logits), _prep("v", v, _REGION_DTYPES)
         B, N, G = logits.shape
         if v.dim() != 3 or v.shape[0] != B or v.shape[1] != N:
@@ -339,9 +339,21 @@ class SoftmaxAttentionPool(torch.autograd.Function):
             first = torch.empty(B, D, device=v.device, dtype=torch.float32) if want_first else None
             extra = (_p(first), float(p_drop), *_seed_args(seed))
             ctx.cfg = (float(p_drop), seed)
-        name, fn = _entry("softmax_attention_pool_drop_fwd" if drop is not None else "softmax_attention_pool_fwd", v.dtype)
-        _launch(name, (B, N, D, G), fn, _p(logits), _p(v), _p(alpha), _p(pooled), *extra, B, N, D, G)
-        ctx.save_for_backward(alpha, v)
+        if lens is not None:
+            # a region count per sample: the `_len_` entry points (the `_drop` semantics on the first lens[b] rows; no
+            # `first` and p_drop = 0 is the plain form)
+            lens = _prep("lens", lens, (torch.int32,))
+            if lens.shape != (B,):
+                raise ValueError("lens must be int32 [B] matching logits [B,N,G]")
+            if drop is None:
+                extra = (None, 0.0, *_seed_args(0))
+            name, fn = _entry("softmax_attention_pool_len_fwd", v.dtype)
+            _launch(name, (B, N, D, G), fn, _p(logits), _p(v), _p(lens), _p(alpha), _p(pooled), *extra, B, N, D, G)
+            ctx.save_for_backward(alpha, v, lens)
+        else:
+            name, fn = _entry("softmax_attention_pool_drop_fwd" if drop is not None else "softmax_attention_pool_fwd", v.dtype)
+            _launch(name, (B, N, D, G), fn, _p(logits), _p(v), _p(alpha), _p(pooled), *extra, B, N, D, G)
+            ctx.save_for_backward(alpha, v)
         ctx.drop = drop is not None
         ctx.set_materialize_grads(False)
         if first is None:
@@ -350,7 +362,7 @@ class SoftmaxAttentionPool(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_alpha, d_pooled, d_first=None):
-        alpha, v = ctx.saved_tensors
+        alpha, v, *lens = ctx.saved_tensors
         B, N, G = alpha.shape
         D = v.shape[2]
         if d_pooled is None:
@@ -359,7 +371,13 @@ class SoftmaxAttentionPool(torch.autograd.Function):
         d_alpha = _prep("grad_alpha", d_alpha) if d_alpha is not None else None
         d_logits = torch.empty_like(alpha)
         d_v = torch.empty_like(v) if ctx.needs_input_grad[1] else None
-        if ctx.drop:
+        if lens:
+            p_drop, seed = ctx.cfg if ctx.drop else (0.0, 0)
+            d_first = _prep("grad_first", d_first) if d_first is not None else None
+            name, fn = _entry("softmax_attention_pool_len_bwd", v.dtype)
+            _launch(name, (B, N, D, G, d_v is not None), fn, _p(alpha), _p(v), _p(lens[0]), _p(d_pooled), _p(d_first), _p(d_alpha),
+                    _p(d_logits), _p(d_v), p_drop, *_seed_args(seed), B, N, D, G)
+        elif ctx.drop:
             p_drop, seed = ctx.cfg
             d_first = _prep("grad_first", d_first) if d_first is not None else None
             name, fn = _entry("softmax_attention_pool_drop_bwd", v.dtype)
@@ -369,11 +387,24 @@ class SoftmaxAttentionPool(torch.autograd.Function):
             name, fn = _entry("softmax_attention_pool_bwd", v.dtype)
             _launch(name, (B, N, D, G, d_v is not None), fn, _p(alpha), _p(v), _p(d_pooled), _p(d_alpha), _p(d_logits),
                     _p(d_v), B, N, D, G)
-        return d_logits, d_v, None
+        return d_logits, d_v, None, None
 
 
-def softmax_attention_pool_drop(logits, v, p_drop=0.0, seed=0, want_first=False):
-    return SoftmaxAttentionPool.apply(logits, v, (p_drop, seed, want_first))
+def softmax_attention_pool_drop(logits, v, p_drop=0.0, seed=0, want_first=False, lens=None):
+    """lens (optional): int32 [B] on v's device, the number of real regions of every sample (see region_counts)."""
+    return SoftmaxAttentionPool.apply(logits, v, (p_drop, seed, want_first), lens)
+
+
+def region_counts(v_len, n_regions, device):
+    """A sample's 'v_len' entry -> the int32 [B] tensor on `device` that the K3 `_len_` kernels read.  A host tensor (the
+    feed's) is validated here: every count must lie in 1..n_regions, else ValueError.  A device tensor is taken as is -- no
+    sync in the step; the kernels clamp what they read."""
+    if not isinstance(v_len, torch.Tensor) or v_len.dim() != 1 or v_len.dtype not in (torch.int32, torch.int64):
+        raise ValueError("v_len must be an int32 or int64 tensor [B] of region counts")
+    if not v_len.is_cuda and v_len.numel() and (int(v_len.min()) < 1 or int(v_len.max()) > n_regions):
+        raise ValueError("v_len holds %d..%d: every region count must lie in 1..%d"
+                         % (int(v_len.min()), int(v_len.max()), n_regions))
+    return v_len.to(device=device, dtype=torch.int32, non_blocking=True).contiguous()
 
 
 class AttentionLogits(torch.autograd.Function):
@@ -2346,8 +2377,8 @@ def pairwise_relation_reduce(v, q1, q2, alpha, glimpse=0, mode=1, dual=False):
     return PairwiseRelationReduce.apply(v, q1, q2, alpha, glimpse, mode, dual)
 
 
-def softmax_attention_pool(logits, v):
-    return SoftmaxAttentionPool.apply(logits, v, None)
+def softmax_attention_pool(logits, v, lens=None):
+    return SoftmaxAttentionPool.apply(logits, v, None, lens)
 
 
 def lowrank_bilinear_fusion(x, h2, weights, biases, gate_dx=False, packed=None):

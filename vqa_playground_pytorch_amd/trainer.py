@@ -441,7 +441,8 @@ class DataParallelTrainer:
     def _model_keys(sample):
         """The entries of a sample dict the models read (config/CoR2.py:203-205): feeder batches also carry the target
         'a' and 'q_id', which must not be cloned / re-copied into the graph's input buffers every step."""
-        return {"v", "q_idxes"} if "q_idxes" in sample else {"v", "q"}
+        keys = {"v", "q_idxes"} if "q_idxes" in sample else {"v", "q"}
+        return keys | {"v_len"} if "v_len" in sample else keys       # per-sample region counts (cor2.Model.forward)
 
     def shard(self, tensor):
         """This rank's contiguous slice of a global-batch tensor (rank r gets [r*B/P, (r+1)*B/P))."""
@@ -461,6 +462,12 @@ class DataParallelTrainer:
         which KLD and BCE are computed directly and CE draws its label per row and step (``last_labels``)."""
         if isinstance(target, dict):
             target = SparseTarget(target["a_idx"], target["a_val"])
+        if self.hip and sample.get("v_len") is not None and sample["v"].is_cuda:
+            # per-sample region counts: validated (a host tensor) and brought to the int32 device form once, so that the graph
+            # path can keep them in a static input buffer like 'v' and 'q_idxes'
+            from . import ops
+            v = sample["v"]
+            sample = dict(sample, v_len=ops.region_counts(sample["v_len"], v.numel() // (v.size(0) * 2048), v.device))
         if self.hip and self.want_graph:
             return self._graph_step(sample, target)
         return self.step_eager(sample, target)
@@ -724,8 +731,10 @@ class DataParallelTrainer:
                 self._capture(sample, target)
             return loss, f.norm_and_coef[0]
         if self.model.training != g["training"] or target.shape != g["target"].shape or any(
-                k not in sample or sample[k].shape != t.shape or sample[k].dtype != t.dtype for k, t in g["sample"].items()):
-            # a batch of another shape (the last one of an epoch), or the model switched between train() and eval() since
+                k not in sample or sample[k].shape != t.shape or sample[k].dtype != t.dtype for k, t in g["sample"].items()) or \
+                ("v_len" in sample) != ("v_len" in g["sample"]):
+            # a batch of another shape (the last one of an epoch), a batch with region counts after a capture without them (the
+            # graph holds the unmasked kernels) or the other way round, or the model switched between train() and eval() since
             # the capture (dropout is baked into the graph): this step is launched kernel by kernel; the captured graphs
             # stay valid for the regular steps that follow
             return self.step_eager(sample, target)
