@@ -390,11 +390,14 @@ extern "C" int vqa_linear_act_bwd(const float* x, int ldx, const float* w, const
   if (rt_dw_ok(M, K, N, ldx, dc.p8)) {
     // register-tile TN form: workgroup = 4 waves x (80 rows of d_w) x 128 columns x one row split; the relu gate (y > 0)
     // and the dropout mask of x are applied to the operands in registers
-    const int S = rt_dw_splits(M);
-    float* slab = static_cast<float*>(workspace);
-    float* dbslab = slab + (size_t)S * N * K;
+    int S = rt_dw_splits(M);
     int rows_per_split = (M + S - 1) / S;
     rows_per_split = (rows_per_split + 15) / 16 * 16;
+    // no empty split (VQA_RT_DW_SPLITS above M / 80): the kernel's row tail of a split that starts past M would start below
+    // m_lo and contract the last M % 16 rows again.  (The workspace query keeps rt_dw_splits(M).)
+    S = (M + rows_per_split - 1) / rows_per_split;
+    float* slab = static_cast<float*>(workspace);
+    float* dbslab = slab + (size_t)S * N * K;
     const rt::TnArgs a{gy, act == 1 ? y : nullptr, x, slab, dbslab, N, ldx, M, N, K, (N + 319) / 320, (K + 127) / 128,
                        rows_per_split};
     const dim3 grid(a.tiles1 * a.tiles2 * S);
