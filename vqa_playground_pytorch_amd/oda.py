@@ -14,11 +14,16 @@ from .layers import MutanFusion, MyATT, MyConv1d, MyLinear, QuestionVectorInput,
 
 
 class Model(nn.Module):
-    def __init__(self, vocab_words=None, num_ans=None, seq2vec=None, regions=36, encoder_dtype=None, encoder_input_dtype=None):
+    def __init__(self, vocab_words=None, num_ans=None, seq2vec=None, regions=36, encoder_dtype=None, encoder_input_dtype=None,
+                 region_counts=False):
         super().__init__()
         self.vocab_words = vocab_words
         self.num_classes = num_ans
         self.regions = regions
+        # opt-in: read sample['v_len'] (int [B], 1..regions) and mask the object-difference kernel and the attention with it.
+        # A different model, not only a faster one: the filter slot conv_att.weight[g, j*310:(j+1)*310] is then trained by the
+        # samples with more than j regions only.  False: the key is refused, as before.
+        self.region_counts = bool(region_counts)
 
         if seq2vec == "skipthoughts":      # the reference's encoder (config/CoR2.py:166), randomly initialised here
             from .encoder import SkipThoughts, encoder_dtype_from, encoder_input_dtype_from
@@ -49,8 +54,9 @@ class Model(nn.Module):
     def stack_groups(self):
         return linear_stack_groups([self.compress_q, self.linear_q])
 
-    def difference_logits(self, v_feature_low, q_feature_low):
-        """config/ODA.py:216-222 + the dropout/1x1-conv of conv_att (config/ODA.py:149), fused (K2)."""
+    def difference_logits(self, v_feature_low, q_feature_low, lens=None):
+        """config/ODA.py:216-222 + the dropout/1x1-conv of conv_att (config/ODA.py:149), fused (K2).
+        lens (optional): int32 [B] device tensor of region counts (ops.region_counts): the masked K2."""
         conv = self.att.conv_att
         p = conv.p if (self.training and conv.p) else 0.0
         seed = 0
@@ -59,7 +65,7 @@ class Model(nn.Module):
             seed = ops.next_dropout_seed()
         w = conv.conv.weight.view(conv.out_channels, -1)
         return ops.object_difference_attention(v_feature_low, q_feature_low, w, conv.conv.bias, p, seed,
-                                               gate_dvl=self.compress_v.grad_pregated)
+                                               gate_dvl=self.compress_v.grad_pregated, lens=lens)
 
     def _grouped_head_ok(self, q_feature, cut):
         """As cor2.Model._grouped_head_ok: the [B,.]-sized layers as grouped phases (head.py)."""
@@ -81,13 +87,23 @@ class Model(nn.Module):
         return logits, cut[0], cut[1]
 
     def forward(self, sample, _cut=None):
-        if "v_len" in sample:
-            # the attention weights of this model are indexed by region slot (fuse_dim = regions * 310): masking them is
-            # the object-difference kernel's business, which takes no counts
-            raise ValueError("ODA.Model takes no per-sample region counts: drop 'v_len' from the sample (CoR2Model masks with it)")
+        if "v_len" in sample and not self.region_counts:
+            # the attention weights of this model are indexed by region slot (fuse_dim = regions * 310): masking them changes
+            # which samples train which slot, so the model reads the counts only when it was built to
+            raise ValueError("ODA.Model takes no per-sample region counts: drop 'v_len' from the sample, or build the model "
+                             "with region_counts=True (CoR2Model masks with it)")
         v = sample["v"]
         b = v.size(0)
         v_feature = v.contiguous().view(b, -1, 2048)
+        # 'v_len' (region_counts=True, optional): the number of real regions of every sample, the rest of its N rows being
+        # (finite) padding.  The masked K2 sums differences over the real rows only and writes exact zeros on the padding, the
+        # masked K3 gives the padding alpha = 0; without the key the model runs unmasked.
+        v_len = sample.get("v_len") if self.region_counts else None
+        if v_len is not None:
+            if not isinstance(v_len, torch.Tensor) or v_len.dim() != 1 or v_len.size(0) != b:
+                raise ValueError("v_len must be [B] = [%d], got %s"
+                                 % (b, tuple(v_len.shape) if isinstance(v_len, torch.Tensor) else type(v_len)))
+            v_len = ops.region_counts(v_len, v_feature.size(1), v_feature.device)
         if v_feature.dtype == torch.bfloat16 and v_feature.is_cuda:      # the feed's bf16 transport format, widened exactly (ops.widen_bf16)
             v_feature = ops.widen_bf16(v_feature)
         if v_feature.size(1) != self.regions:
@@ -111,8 +127,8 @@ class Model(nn.Module):
             # the two MyLinear(2400 -> 310) on the question vector (config/ODA.py:185,193 applied at :207,:233): one batched GEMM
             q_both = my_linears([self.compress_q, self.linear_q], q_feature, group_first=True)   # [2,B,310]
             q_feature_low, q_final = ops.split_groups(q_both, (1, 1))                              # views; one cat kernel backward
-        logits = self.difference_logits(v_feature_low, q_feature_low)
-        v_final, alphas, _ = self.att.attend(v_feature, logits, grouped=grouped)
+        logits = self.difference_logits(v_feature_low, q_feature_low, lens=v_len)
+        v_final, alphas, _ = self.att.attend(v_feature, logits, grouped=grouped, lens=v_len)
 
         self.alpha_dict = {"alphas": alphas[0].detach()}
         if grouped:

@@ -876,41 +876,62 @@ class LowRankBilinearFusionBf16(torch.autograd.Function):
 class ObjectDifferenceAttention(torch.autograd.Function):
     """K2.  logits[b,i,g] = bias[g] + sum_{j,d} w[g,j*L+d] * keep * (vl[b,i,d]-vl[b,j,d]) * ql[b,d].
     Replaces config/ODA.py:216-222 + the dropout and 1x1 conv of config/ODA.py:149.
-    gate_dvl: vl is the relu output of the layer in front and nothing else reads it; d_vl comes back multiplied by (vl > 0)."""
+    gate_dvl: vl is the relu output of the layer in front and nothing else reads it; d_vl comes back multiplied by (vl > 0).
+    lens (optional): int32 [B] on vl's device, the number of real regions of every sample -- sums over i, j < lens[b], logits and
+    d_vl exactly 0 on the padding, which is never read."""
 
     @staticmethod
-    def forward(ctx, vl, ql, w, bias, p_drop, seed, gate_dvl=False):
+    def forward(ctx, vl, ql, w, bias, p_drop, seed, gate_dvl=False, lens=None):
         vl, ql, w, bias = _prep("vl", vl), _prep("ql", ql), _prep("w", w), _prep("bias", bias)
         B, N, L = vl.shape
         G = bias.shape[0]
         if ql.shape != (B, L) or w.numel() != G * N * L:
             raise ValueError("object_difference_attention: ql must be [B,L], w must hold G*N*L = %d values (got %d)"
                              % (G * N * L, w.numel()))
+        if lens is not None:
+            # a region count per sample: the `_len_` entry points (csrc/object_difference_masked.hip) read it on the device
+            if (not isinstance(lens, torch.Tensor) or lens.dtype != torch.int32 or lens.shape != (B,)
+                    or lens.device != vl.device):
+                raise ValueError("object_difference_attention: lens must be int32 [B] = [%d] on %s (see region_counts)"
+                                 % (B, vl.device))
+            lens = lens.contiguous()
         logits = torch.empty(B, N, G, device=vl.device, dtype=torch.float32)
         sv, sp = _seed_args(seed)
-        _launch("object_difference_attention_fwd", (B, N, L, G, float(p_drop) > 0),
-                _lib.lib().vqa_object_difference_attention_fwd, _p(vl), _p(ql), _p(w), _p(bias), _p(logits),
-                float(p_drop), sv, sp, B, N, L, G)
-        ctx.save_for_backward(vl, ql, w)
+        if lens is not None:
+            _launch("object_difference_attention_len_fwd", (B, N, L, G, float(p_drop) > 0),
+                    _lib.lib().vqa_object_difference_attention_len_fwd, _p(vl), _p(ql), _p(w), _p(bias), _p(lens),
+                    _p(logits), float(p_drop), sv, sp, B, N, L, G)
+            ctx.save_for_backward(vl, ql, w, lens)
+        else:
+            _launch("object_difference_attention_fwd", (B, N, L, G, float(p_drop) > 0),
+                    _lib.lib().vqa_object_difference_attention_fwd, _p(vl), _p(ql), _p(w), _p(bias), _p(logits),
+                    float(p_drop), sv, sp, B, N, L, G)
+            ctx.save_for_backward(vl, ql, w)
         ctx.bias = bias
         ctx.cfg = (float(p_drop), seed, G, bool(gate_dvl))
         return logits
 
     @staticmethod
     def backward(ctx, d_logits):
-        vl, ql, w = ctx.saved_tensors
+        vl, ql, w, *lens = ctx.saved_tensors
         p_drop, seed, G, gate_dvl = ctx.cfg
         B, N, L = vl.shape
         d_logits = _prep("grad_logits", d_logits)
         d_vl, d_ql, d_w = torch.empty_like(vl), torch.empty_like(ql), _grad_like(w)
         d_bias = _grad_like(ctx.bias)
         L_ = _lib.lib()
-        ws, ws_bytes = _workspace(L_.vqa_object_difference_attention_bwd_workspace_bytes, B, N, L, G, device=vl.device)
         sv, sp = _seed_args(seed)
+        if lens:
+            ws, ws_bytes = _workspace(L_.vqa_object_difference_attention_len_bwd_workspace_bytes, B, N, L, G, device=vl.device)
+            _launch("object_difference_attention_len_bwd", (B, N, L, G, p_drop > 0), L_.vqa_object_difference_attention_len_bwd,
+                    _p(vl), _p(ql), _p(w), _p(d_logits), _p(lens[0]), _p(d_vl), _p(d_ql), _p(d_w), _p(d_bias), _p(ws), ws_bytes,
+                    p_drop, sv, sp, B, N, L, G, int(gate_dvl))
+            return d_vl, d_ql, d_w, d_bias, None, None, None, None
+        ws, ws_bytes = _workspace(L_.vqa_object_difference_attention_bwd_workspace_bytes, B, N, L, G, device=vl.device)
         _launch("object_difference_attention_bwd", (B, N, L, G, p_drop > 0), L_.vqa_object_difference_attention_bwd,
                 _p(vl), _p(ql), _p(w), _p(d_logits), _p(d_vl), _p(d_ql), _p(d_w), _p(d_bias), _p(ws), ws_bytes,
                 p_drop, sv, sp, B, N, L, G, int(gate_dvl))
-        return d_vl, d_ql, d_w, d_bias, None, None, None
+        return d_vl, d_ql, d_w, d_bias, None, None, None, None
 
 
 def f32_products():
@@ -2389,5 +2410,6 @@ def lowrank_bilinear_fusion(x, h2, weights, biases, gate_dx=False, packed=None):
     return LowRankBilinearFusion.apply(x, h2, gate_dx, *weights, *biases)
 
 
-def object_difference_attention(vl, ql, w, bias, p_drop=0.0, seed=0, gate_dvl=False):
-    return ObjectDifferenceAttention.apply(vl, ql, w, bias, p_drop, seed, gate_dvl)
+def object_difference_attention(vl, ql, w, bias, p_drop=0.0, seed=0, gate_dvl=False, lens=None):
+    """lens (optional): int32 [B] on vl's device, the number of real regions of every sample (see region_counts)."""
+    return ObjectDifferenceAttention.apply(vl, ql, w, bias, p_drop, seed, gate_dvl, lens)
