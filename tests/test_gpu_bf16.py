@@ -16,19 +16,14 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_harness import EPS_BF16, dev
 from oracle import kernels_np as K
 from oracle import seeded
 
 pytestmark = pytest.mark.gpu
 
-EPS_BF16 = 2.0 ** -8
 RTOL_F32 = 2e-4
 RTOL_MID = 2e-2
-
-
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
 
 
 def bf_round(a):

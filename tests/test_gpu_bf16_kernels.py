@@ -13,7 +13,7 @@ at a handful of shapes; here
        A3 K4 as R GEMMs through the C ABI: fwd2 / generic forward, every prep kernel, gate_dx, d_x = NULL, phases 1 + 2 == 3
        A4 K4 rank-folded through the C ABI: every NB 1..8 and (LBW, NCH) instantiation, H % 256 != 0, empty and one-sample slabs
        A5 vqa_pack_bf16 / ShadowPlan.pack: plain, transposed (several 32 x 32 tiles, partial ones), offsets, both kinds, ties
-  B  random bf16 operands against float64 with the project's bar (Bars, restated from tests/test_gpu_encoder_bf16.py): four times
+  B  random bf16 operands against float64 with the project's bar (Bars: WorstBar of tests/kernel_harness.py): four times
      the error of the same formula in float32 with torch on the CPU plus one float32 ulp; bf16 outputs elementwise within
      2^-8 |ref| + that bar x scale.  The bf16 intermediates are REMOVED from the comparison: the R-GEMM backward's reference reads
      the kernel's own h1 and forms bf16(float32(g * h2)) as the kernel does; the fold draws h2 from +-{1/4 .. 4}, so that the folded
@@ -47,158 +47,20 @@ import functools
 import pytest
 import torch
 
+from kernel_harness import (BF, E_BADARG, E_UNSUPPORTED, INF, NAN, SENT, WorstBar as Bars, _amax, _below_2_24, _dbf, _logged, _names, _ptr,
+                            _ptrs, _same_bits, _sentinel, _take, _untouched, assert_exact, dev, ops)  # noqa: F401  (ops: the fixture)
+
 pytestmark = pytest.mark.gpu
-SENT = -12345.0
-E_BADARG, E_UNSUPPORTED = -1, -2
-EPS32 = float(torch.finfo(torch.float32).eps)
-EPS_BF16 = 2.0 ** -8
-BF = torch.bfloat16
-NAN, INF = float("nan"), float("inf")
 TILES = [None, "128x128", "128x64", "64x128", "64x64"]
 _tile_id = lambda t: "tile-" + (t or "default")      # noqa: E731
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vqa_playground_pytorch_amd import _lib, ops as o
-    _lib.lib()
-    return o
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16 if t.dtype == BF else torch.int32)
-
-
-def _same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(_bits(a), _bits(b))
-
-
-def _ptr(t, off=0):
-    return ctypes.c_void_p(t.data_ptr() + t.element_size() * int(off)) if t is not None else None
-
-
-def _ptrs(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
-def _sentinel(*shape, dtype=torch.float32):
-    return torch.full(shape, SENT, device=dev(), dtype=dtype)
-
-
-def _untouched(t):
-    return bool((_bits(t) == _bits(torch.full((1,), SENT, device=t.device, dtype=t.dtype))).all())
-
-
-def _take(buf, window, what):
-    """-> a copy of buf[window]; asserts that nothing else of the sentinel-filled `buf` changed"""
-    got = buf[window].clone()
-    buf[window] = SENT
-    assert _untouched(buf), "%s: a store outside the output window" % what
-    return got
-
-
-def _logged(L, call):
-    """run `call` -> [(kernel expression without blanks, grid in work-items)] of the launches it made"""
-    L.vqa_launch_log_reset()
-    call()
-    buf = (ctypes.c_ulonglong * 16)()
-    n = L.vqa_launch_log(buf, 16)
-    return [((L.vqa_launch_log_kernel(i) or b"").decode().replace(" ", ""), int(buf[i])) for i in range(min(n, 16))]
-
-
-def _names(log):
-    return [k for k, _ in log]
 
 
 def _ints(gen, *shape, lo=-4, hi=4):
     return torch.randint(lo, hi + 1, shape, generator=gen)
 
 
-def _dbf(t):
-    """CPU tensor of bf16-exact values -> bf16 on the GPU"""
-    out = t.to(torch.float32).to(BF)
-    assert torch.equal(out.to(torch.float64), t.to(torch.float64)), "the operand is not exact in bf16"
-    return out.to(dev()).contiguous()
-
-
 def _df(t):
     return t.to(torch.float32).to(dev()).contiguous()
-
-
-def _below_2_24(*bounds):
-    for b in bounds:
-        assert int(b) < 2 ** 24, "a sum of this case can leave the exact range of fp32: bound %d" % int(b)
-
-
-def _amax(t):
-    return int(t.abs().max())
-
-
-def _canon(t):
-    """the kernel's result on the CPU as fp32 with -0.0 folded into 0.0 (the integer reference has one zero)"""
-    return t.detach().float().cpu() + 0.0
-
-
-def assert_exact(name, got, ref):
-    """got (fp32 or bf16 GPU tensor) against the int64 reference: fp32 bit for bit, bf16 == ref.float().to(bf16) bit for bit"""
-    assert ref.dtype == torch.int64 and tuple(got.shape) == tuple(ref.shape), (name, got.dtype, tuple(got.shape), tuple(ref.shape))
-    _below_2_24(_amax(ref))
-    want = ref.float()
-    if got.dtype == BF:
-        want = want.to(BF).float()
-    else:
-        assert got.dtype == torch.float32, (name, got.dtype)
-    have = _canon(got)
-    if not torch.equal(_bits(have), _bits(want)):
-        bad = (_bits(have) != _bits(want)).nonzero()
-        first = tuple(int(i) for i in bad[0])
-        raise AssertionError("%s: %d of %d elements differ from the integer reference; first at %s: got %r, want %r"
-                             % (name, len(bad), want.numel(), first, float(have[first]), float(want[first])))
-
-
-class Bars:
-    """kernel error against float64, relative to the tensor's largest magnitude; bar: four times the error of the same formulas
-    in float32 with torch on the CPU, plus one float32 ulp of that magnitude.  A bf16 result: elementwise within
-    2^-8 |ref| + that bar x the magnitude (one rounding of a value that carries the fp32 error)."""
-
-    def __init__(self):
-        self.worst = (-1.0, 0.0, 0.0, "")
-
-    def _bar(self, name, got, ref64, ref32):
-        got = got.detach().cpu()
-        assert got.shape == ref64.shape, (name, got.shape, ref64.shape)
-        assert bool(torch.isfinite(got).all()), name
-        mag = float(ref64.abs().max())
-        assert mag > 0.0, name
-        e32 = float((ref32.double() - ref64).abs().max()) / mag
-        return got.double(), mag, e32, 4.0 * e32 + EPS32
-
-    def _note(self, name, err, e32, bar):
-        print("[%s] kernel %.3e  float32 torch %.3e  bar %.3e" % (name, err, e32, bar))
-        if err / bar > self.worst[0]:
-            self.worst = (err / bar, err, bar, name)
-
-    def check(self, name, got, ref64, ref32):
-        assert got.dtype == torch.float32, (name, got.dtype)
-        g, mag, e32, bar = self._bar(name, got, ref64, ref32)
-        err = float((g - ref64).abs().max()) / mag
-        self._note(name, err, e32, bar)
-        assert err <= bar, (name, err, e32, bar)
-
-    def check_bf16(self, name, got, ref64, ref32):
-        """reported: the largest |err| - 2^-8 |ref| over the magnitude, against the fp32 bar"""
-        assert got.dtype == BF, (name, got.dtype)
-        g, mag, e32, bar = self._bar(name, got, ref64, ref32)
-        excess = float(((g - ref64).abs() - EPS_BF16 * ref64.abs()).max()) / mag
-        self._note(name, max(excess, 0.0), e32, bar)
-        assert excess <= bar, (name, excess, e32, bar)
-
-    def report(self, measured, tag):
-        measured("%s err / max|ref|" % tag, self.worst[1], self.worst[2], self.worst[3])
 
 
 # ======================================================================================================================= A1: NT

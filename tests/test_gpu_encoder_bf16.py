@@ -9,84 +9,24 @@
   model level     CoR2 with the bf16 encoder: eval logits next to the fp32 encoder's, the graph-replayed train step, the evaluator
 
 Bars: fp32 results of one kernel: four times the error of the same formulas in float32 with torch on the CPU plus one float32
-ulp (the rule of tests/test_gpu_encoder_kernels.py::GateBars, restated here); results that pass through a bf16 intermediate:
-2e-2 of the tensor's scale (RTOL_MID of tests/test_gpu_bf16.py)."""
+ulp (WorstBar of tests/kernel_harness.py, the rule of tests/test_gpu_encoder_kernels.py::GateBars); results that pass through a
+bf16 intermediate: 2e-2 of the tensor's scale (RTOL_MID of tests/test_gpu_bf16.py)."""
 import ctypes
 import functools
 
 import pytest
 import torch
 
+from kernel_harness import (BF, EPS_BF16, E_BADARG, E_UNSUPPORTED, SENT, WorstBar as Bars, _ptr, _same_bits, _sentinel, _untouched, dev,
+                            ops)  # noqa: F401  (ops: the fixture)
+
 gpu = pytest.mark.gpu
-SENT = -12345.0
-E_BADARG, E_UNSUPPORTED = -1, -2
-EPS32 = float(torch.finfo(torch.float32).eps)
-EPS_BF16 = 2.0 ** -8
 RTOL_F32 = 2e-4
 RTOL_MID = 2e-2
-BF = torch.bfloat16
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vqa_playground_pytorch_amd import _lib, ops as o
-    _lib.lib()
-    return o
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16 if t.dtype == BF else torch.int32)
-
-
-def _same_bits(a, b):
-    return a.dtype == b.dtype and torch.equal(_bits(a), _bits(b))
-
-
-def _ptr(t, off=0):
-    return ctypes.c_void_p(t.data_ptr() + t.element_size() * int(off)) if t is not None else None
-
-
-def _sentinel(*shape, dtype=torch.float32):
-    return torch.full(shape, SENT, device=dev(), dtype=dtype)
-
-
-def _untouched(t):
-    return bool((_bits(t) == _bits(torch.full((1,), SENT, device=t.device, dtype=t.dtype))).all())
 
 
 def pad64(n):
     return (n + 63) // 64 * 64
-
-
-class Bars:
-    """kernel error against float64, relative to the tensor's largest magnitude; bar: four times the error of the same formulas
-    in float32 with torch on the CPU, plus one float32 ulp of that magnitude"""
-
-    def __init__(self):
-        self.worst = (-1.0, 0.0, 0.0, "")
-
-    def check(self, name, got, ref64, ref32):
-        got = got.cpu()
-        assert got.shape == ref64.shape, (name, got.shape, ref64.shape)
-        assert bool(torch.isfinite(got).all()), name
-        mag = float(ref64.abs().max())
-        if mag == 0.0:
-            assert not bool(got.any()), name
-            return
-        err = float((got.double() - ref64).abs().max()) / mag
-        e32 = float((ref32.double() - ref64).abs().max()) / mag
-        bar = 4.0 * e32 + EPS32
-        print("[%s] kernel %.3e  float32 torch %.3e  bar %.3e" % (name, err, e32, bar))
-        if err / bar > self.worst[0]:
-            self.worst = (err / bar, err, bar, name)
-        assert err <= bar, (name, err, e32, bar)
-
-    def report(self, measured, tag):
-        measured("%s err / max|ref|" % tag, self.worst[1], self.worst[2], self.worst[3])
 
 
 # ---- 1-3. the GEMM -------------------------------------------------------------------------------------------------------------------

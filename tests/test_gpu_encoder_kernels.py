@@ -18,42 +18,17 @@ import ctypes
 import pytest
 import torch
 
+from kernel_harness import (EPS32, E_BADARG, E_UNSUPPORTED, INF, NAN, SENT, _bits, _ptr, _same_bits, _sentinel, _untouched, dev,
+                            ops)  # noqa: F401  (ops: the fixture)
 from vqa_playground_pytorch_amd.encoder import BayesianGRU
 
 gpu = pytest.mark.gpu
-SENT = -12345.0
-E_BADARG, E_UNSUPPORTED = -1, -2
 MAX_BAR, RMS_FACTOR = 4e-6, 2.0          # tests/test_gpu_split.py::_compare_with_engine
-EPS32 = float(torch.finfo(torch.float32).eps)
-INF, NAN = float("inf"), float("nan")
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vqa_playground_pytorch_amd import _lib, ops as o
-    _lib.lib()
-    return o
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
 
 
 def _classes(t):
     """0 finite, 1 +Inf, 2 -Inf, 3 NaN"""
     return torch.where(torch.isnan(t), 3, torch.where(torch.isposinf(t), 1, torch.where(torch.isneginf(t), 2, 0)))
-
-
-def _ptr(t, off=0):
-    return ctypes.c_void_p(t.data_ptr() + 4 * int(off))
 
 
 def _dev(t):
@@ -617,14 +592,6 @@ class GateBars:
 
     def report(self, measured, tag):
         measured("%s err / max|ref|" % tag, self.worst[1], self.worst[2], self.worst[3])
-
-
-def _sentinel(*shape):
-    return torch.full(shape, SENT, device=dev(), dtype=torch.float32)
-
-
-def _untouched(t):
-    return bool((_bits(t) == _bits(torch.full((1,), SENT, device=t.device))).all())
 
 
 def _steps(T):

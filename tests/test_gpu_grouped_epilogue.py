@@ -20,18 +20,13 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_harness import E_BADARG, E_UNSUPPORTED, SENT, dev
+
 pytestmark = pytest.mark.gpu
 RTOL = 2e-4            # fp32 products against float64, on the output's scale (tests/test_gpu_head.py)
-SENT = -12345.0
 U = 2.0 ** -24         # fp32 unit roundoff
 SUM, LINEAR, RANK_PRODUCT, GRAD, RANK_PRODUCT_BWD = 0, 1, 2, 3, 4
 NT, NN, TN, NN_A4, TN_A4 = 0, 1, 2, 3, 4
-E_BADARG, E_UNSUPPORTED = -1, -2
-
-
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def mods():

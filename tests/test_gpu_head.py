@@ -7,15 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_harness import dev
 from oracle import seeded
 
 pytestmark = pytest.mark.gpu
 RTOL = 2e-4      # fp32 MFMA products against float64, on the output's scale
-
-
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def g(a, grad=False):

@@ -12,7 +12,7 @@ and the dispatchers' arithmetic) says that it was, and its result is compared wh
      itself in test_reference_is_the_oracle).  Outputs sit in sentinel-filled buffers that are compared whole, inputs in NaN-padded
      ones (ldx = L + 2 leaves a NaN gap behind every row of x), the workspace is exactly *_workspace_bytes long (restated here),
      pre-filled with NaN, with a sentinel fence behind it.  gate_dx = 1 gives the ungated d_x times (x > 0).
-  B  random operands against float64 (oracle/kernels_np.py) under the project's bar (restated from tests/test_gpu_region_kernels.py):
+  B  random operands against float64 (oracle/kernels_np.py) under the project's bar (Bars of tests/kernel_harness.py):
      four times the error of the same formula in float32 with torch on the CPU plus one float32 ulp of the tensor's largest
      magnitude.  Every case reports what it measured.  The split engine reports against the same bar and is held to it or to the
      bar test_lowrank_bilinear_fusion_large_batch_against_torch_fp64 states for it (2e-5 of the largest magnitude).
@@ -58,22 +58,18 @@ Dispatch form (as the source spells the launch site) -> the test that launches i
 import ctypes
 import functools
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+from kernel_harness import (E_BADARG, E_UNSUPPORTED, F64, NAN, PAD, Bars, _below_2_24, _call, _ceil, _in, _out, _ptr, _sentinel, _untouched,
+                            _win, assert_exact, dev, launch_sites, ops, set_knobs, spell)  # noqa: F401  (ops: the fixture)
+
 gpu = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vqa_playground_pytorch_amd", "csrc")
 K4_FILES = ("bilinear_fusion.hip", "bilinear_folded.hip", "bilinear_rt.hip", "bilinear_dw_rt.hip", "bilinear_dw_split.hip")
-SENT = -12345.0
-E_BADARG, E_UNSUPPORTED = -1, -2
-EPS32 = float(torch.finfo(torch.float32).eps)
-F32, F64 = torch.float32, torch.float64
-NAN = float("nan")
-PAD = 8                 # elements of sentinel (outputs) or NaN (inputs) in front of and behind every window: 32 bytes
 
 # ---- the launch sites as the source spells them (blanks removed); a macro parameter (NAME_) arrives substituted in the log -------
 S_FWD, S_DX, S_DW = "(bilinear_fwd_kernel<BM_,BN_,BK_>)", "(bilinear_dx_kernel<BM_,BN_,BK_>)", "(bilinear_dw_kernel<BM_,BN_,BK_>)"
@@ -86,100 +82,12 @@ S_RT1, S_RT22, S_RT24, S_RT2 = ("(bilinear_fold_rt_kernel<FWD,S,IB,1>)", "(bilin
 S_DWRT, S_DWRT_TUNE = "(bilinear_dw_rt_kernel<R_,NS_,D_>)", "(bilinear_dw_rt_kernel<2,9,9,4>)"
 S_SPLIT = "(bilinear_dw_split_kernel<LBW_>)"
 MACRO_PARAMS = ("BM_", "BN_", "BK_", "PF_", "R_", "NB_", "W_", "OB_", "NS_", "LBW_")     # (D_ is a constant of the launcher, not a parameter)
-
-
-def spell(site, *values):
-    """the log's spelling of a launch site: its macro parameters replaced, in order, by `values`"""
-    vals = list(values)
-    out = re.sub(r"\b(%s)(?=[,>])" % "|".join(MACRO_PARAMS), lambda m: str(vals.pop(0)), site)
-    assert not vals, (site, values)
-    return out
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vqa_playground_pytorch_amd import _lib, ops as o
-    _lib.lib()
-    return o
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _ptr(t, off=0):
-    return ctypes.c_void_p(t.data_ptr() + t.element_size() * int(off)) if t is not None else None
+spell = functools.partial(spell, params=MACRO_PARAMS)
 
 
 def _pp(bufs, off=PAD):
     """host array of device pointers, one per rank"""
     return (ctypes.c_void_p * len(bufs))(*[b.data_ptr() + 4 * off for b in bufs])
-
-
-def _sentinel(*shape):
-    return torch.full(shape, SENT, device=dev(), dtype=F32)
-
-
-def _untouched(t):
-    return bool((_bits(t) == _bits(torch.full((1,), SENT, device=t.device, dtype=t.dtype))).all())
-
-
-def _out(n):
-    """a sentinel-filled buffer with an n-element output window PAD elements in"""
-    buf = _sentinel(n + 2 * PAD)
-    assert buf.data_ptr() % 16 == 0
-    return buf
-
-
-def _win(buf, shape, what):
-    """-> a copy of the window; asserts that nothing else of the sentinel-filled `buf` changed"""
-    n = int(np.prod(shape))
-    got = buf[PAD:PAD + n].clone()
-    buf[PAD:PAD + n] = SENT
-    assert _untouched(buf), "%s: a store outside the output window" % what
-    return got.view(*shape)
-
-
-def _in(t, ld=None):
-    """CPU tensor -> an fp32 GPU buffer that holds it PAD elements in, NaN on both sides; with ld: its rows (last dimension) at
-    stride ld, NaN in the gap.  A read outside the window that is USED poisons an output"""
-    cols = t.shape[-1]
-    rows = t.reshape(-1, cols).to(F32)
-    ld = cols if ld is None else ld
-    buf = torch.full((rows.shape[0] * ld + 2 * PAD,), NAN, dtype=F32)
-    buf[PAD:PAD + rows.shape[0] * ld].view(rows.shape[0], ld)[:, :cols] = rows
-    return buf.to(dev())
-
-
-def _logged(L, call):
-    """run `call` -> [(kernel expression without blanks, grid in work-items)] of the launches it made"""
-    L.vqa_launch_log_reset()
-    call()
-    buf = (ctypes.c_ulonglong * 16)()
-    n = L.vqa_launch_log(buf, 16)
-    return [((L.vqa_launch_log_kernel(i) or b"").decode().replace(" ", ""), int(buf[i])) for i in range(min(n, 16))]
-
-
-def _call(ops, fn, *args):
-    """one C-ABI call on torch's current stream -> (return code, launch log), synchronised"""
-    L = ops._lib.lib()
-    rc = []
-    log = _logged(L, lambda: rc.append(fn(*args, ops._stream())))
-    torch.cuda.synchronize()
-    return rc[0], log
-
-
-def _ceil(a, b):
-    return -(-a // b)
-
-
-def set_knobs(lib_option, knobs):
-    for k, v in knobs:
-        lib_option(k, v)
 
 
 # ======================================================================================================================= the dispatchers, restated
@@ -373,11 +281,6 @@ def amplitude(B, N, L, H, R):
     raise AssertionError("no amplitude keeps this shape exact")
 
 
-def _below_2_24(*bs):
-    for b in bs:
-        assert int(b) < 2 ** 24, "a sum of this case can leave the exact range of fp32: bound %d" % int(b)
-
-
 @functools.lru_cache(maxsize=2)
 def operands(B, N, L, H, R, amp, nonneg):
     """float64 integers on the CPU: x [B,N,L] (within [0, amp], about half of it 0, if nonneg), w1 [R,H,L], b1 [R,H], h2 [B,R,H], g [B,N,H]"""
@@ -431,19 +334,6 @@ def test_reference_is_the_oracle():
     for key, want in zip(("out", "h1", "d_x", "d_w1", "d_b1", "d_h2"), (out, h1) + tuple(knp.lowrank_bilinear_fusion_bwd(*np_in))):
         assert np.array_equal(res[key].numpy(), want), key
     assert float(res["d_x"].abs().max()) > 0 and float(operands(B, N, L, H, R, 3, True)[0].min()) == 0.0
-
-
-def assert_exact(name, got, ref):
-    """got (fp32 GPU tensor) against the float64 integer reference, bit for bit (-0.0 counts as 0.0: an integer has one zero)"""
-    assert got.dtype == F32 and tuple(got.shape) == tuple(ref.shape), (name, got.dtype, tuple(got.shape), tuple(ref.shape))
-    assert bool((ref == ref.round()).all())
-    _below_2_24(int(ref.abs().max()))
-    have = got.detach().cpu().to(F64)
-    if not torch.equal(have, ref):           # (value equality: -0.0 == 0.0, NaN != anything)
-        bad = (have != ref).nonzero()
-        first = tuple(int(i) for i in bad[0])
-        raise AssertionError("%s: %d of %d elements differ from the integer reference; first at %s: got %r, want %r"
-                             % (name, len(bad), ref.numel(), first, float(have[first]), float(ref[first])))
 
 
 # ======================================================================================================================= the calls
@@ -764,29 +654,6 @@ def test_case_tables_reach_every_instantiation():
 
 
 # ======================================================================================================================= B
-class Bars:
-    """kernel error against float64 over the tensor's largest magnitude; bar: four times the error of the same formulas in float32
-    with torch on the CPU, plus one float32 ulp.  Every figure is kept and reported through `measured`; close() fails if one missed
-    its bar (`fallback`: the bar the project already states for that output, where the first one is missed)."""
-
-    def __init__(self, measured, case):
-        self.measured, self.case, self.rows = measured, case, []
-
-    def check(self, name, got, ref64, ref32, fallback=None):
-        got = got.detach().cpu()
-        assert got.shape == ref64.shape and got.dtype == F32, (self.case, name, got.shape, ref64.shape)
-        mag = float(ref64.abs().max())
-        assert mag > 0.0, (self.case, name)
-        bar = 4.0 * float((ref32.double() - ref64).abs().max()) / mag + EPS32
-        err = float((got.double() - ref64).abs().max()) / mag if bool(torch.isfinite(got).all()) else float("inf")
-        self.rows.append((err, bar, name, fallback))
-        self.measured("%s %s" % (self.case, name), err, bar)
-
-    def close(self):
-        missed = [r for r in self.rows if not (r[0] <= r[1] or (r[3] is not None and r[0] <= r[3]))]
-        assert not missed, (self.case, [(n, "%.3e > %.3e" % (e, b)) for e, b, n, _ in missed])
-
-
 SPLIT_BAR = 2e-5      # test_lowrank_bilinear_fusion_large_batch_against_torch_fp64's bar for the split engine's gradients
 # (id, entry, B, N, L, H, R, knobs, forward form, forms that must be in the backward's log)
 RANDOM_CASES = [
@@ -990,19 +857,6 @@ def test_refusals_launch_nothing(ops, lib_option):
 
 
 # ======================================================================================================================= D
-def launch_sites(path):
-    """the first argument of every VQA_LAUNCH( of a source file, blanks removed"""
-    text = open(path).read()
-    found = []
-    for m in re.finditer(r"\bVQA_LAUNCH\(", text):
-        depth, i = 0, m.end()
-        while depth or text[i] != ",":
-            depth += {"(": 1, ")": -1}.get(text[i], 0)
-            i += 1
-        found.append(re.sub(r"\s+", "", text[m.end():i]))
-    return found
-
-
 def test_every_launch_site_is_declared():
     """a launch site added to (or renamed in) one of the five files without a case here fails; so does a case whose site no longer
     exists.  The diagnostic VQA_K4_DW_TUNE site is declared and not launched"""

@@ -15,7 +15,7 @@ and its result is compared whole.
      (ldx > K leaves a NaN gap behind every row of x), the workspace is exactly *_workspace_bytes long (restated here), NaN-filled,
      with a sentinel fence behind it.  d_x = NULL, d_b = NULL, bias = NULL, gz_out present / absent each appear.
   B  random operands against float64 (oracle/kernels_np.py; the exported mask; the kernel's own y as the gate) under the project's
-     bar (restated from tests/test_gpu_k4_kernels.py): four times the error of the same formula in float32 with torch on the CPU
+     bar (Bars of tests/kernel_harness.py): four times the error of the same formula in float32 with torch on the CPU
      plus one float32 ulp of the tensor's largest magnitude.  The split engine reports against the same bar and is held to it or to
      the bar tests/test_gpu_split.py states for it (2e-5 of the largest magnitude).  One case runs p = 0.3.
   C  a NaN in a row of x or gy stays in that row of y / d_x (rows at tile and split edges); a NaN in a DROPPED element of x: the
@@ -69,22 +69,18 @@ Dispatch form (as the source spells the launch site) -> the test that launches i
 import ctypes
 import functools
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+from kernel_harness import (E_BADARG, E_UNSUPPORTED, F64, NAN, PAD, Bars, _below_2_24, _call, _ceil, _in, _out, _ptr, _sentinel, _untouched,
+                            _win, assert_exact, dev, launch_sites, ops, set_knobs, spell)  # noqa: F401  (ops: the fixture)
+
 gpu = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vqa_playground_pytorch_amd", "csrc")
 K5_FILES = ("linear_act.hip", "linear_split.hip")
-SENT = -12345.0
-E_BADARG, E_UNSUPPORTED = -1, -2
-EPS32 = float(torch.finfo(torch.float32).eps)
-F32, F64 = torch.float32, torch.float64
-NAN = float("nan")
-PAD = 8                 # elements of sentinel (outputs) or NaN (inputs) in front of and behind every window: 32 bytes
 SEED = 4242
 AMP = 3                 # |operand| <= 3
 
@@ -109,99 +105,11 @@ S_TNW, S_TNW_D = "(sp::gemm_tn_kernel<NA,SPN,false>)", "(sp::gemm_tn_kernel<NA,S
 S_TNR, S_TNR_D = "(sp::gemm_tn_shared_kernel<NA,false,0,true>)", "(sp::gemm_tn_shared_kernel<NA,true,0,true>)"
 S_SUM = "(sp::slab_sum_kernel)"
 MACRO_PARAMS = ("BM_", "BN_", "PF_")
-
-
-def spell(site, *values):
-    """the log's spelling of a launch site: its macro parameters replaced, in order, by `values`"""
-    vals = list(values)
-    out = re.sub(r"\b(%s)(?=[,>])" % "|".join(MACRO_PARAMS), lambda m: str(vals.pop(0)), site)
-    assert not vals, (site, values)
-    return out
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vqa_playground_pytorch_amd import _lib, ops as o
-    _lib.lib()
-    return o
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _ptr(t, off=0):
-    return ctypes.c_void_p(t.data_ptr() + t.element_size() * int(off)) if t is not None else None
-
-
-def _sentinel(*shape):
-    return torch.full(shape, SENT, device=dev(), dtype=F32)
-
-
-def _untouched(t):
-    return bool((_bits(t) == _bits(torch.full((1,), SENT, device=t.device, dtype=t.dtype))).all())
-
-
-def _out(n):
-    """a sentinel-filled buffer with an n-element output window PAD elements in"""
-    buf = _sentinel(n + 2 * PAD)
-    assert buf.data_ptr() % 16 == 0
-    return buf
-
-
-def _win(buf, shape, what):
-    """-> a copy of the window; asserts that nothing else of the sentinel-filled `buf` changed"""
-    n = int(np.prod(shape))
-    got = buf[PAD:PAD + n].clone()
-    buf[PAD:PAD + n] = SENT
-    assert _untouched(buf), "%s: a store outside the output window" % what
-    return got.view(*shape)
-
-
-def _in(t, ld=None):
-    """CPU tensor -> an fp32 GPU buffer that holds it PAD elements in, NaN on both sides; with ld: its rows (last dimension) at
-    stride ld, NaN in the gap.  A read outside the window that is USED poisons an output"""
-    cols = t.shape[-1]
-    rows = t.reshape(-1, cols).to(F32)
-    ld = cols if ld is None else ld
-    buf = torch.full((rows.shape[0] * ld + 2 * PAD,), NAN, dtype=F32)
-    buf[PAD:PAD + rows.shape[0] * ld].view(rows.shape[0], ld)[:, :cols] = rows
-    return buf.to(dev())
-
-
-def _logged(L, call):
-    """run `call` -> [(kernel expression without blanks, grid in work-items)] of the launches it made"""
-    L.vqa_launch_log_reset()
-    call()
-    buf = (ctypes.c_ulonglong * 16)()
-    n = L.vqa_launch_log(buf, 16)
-    return [((L.vqa_launch_log_kernel(i) or b"").decode().replace(" ", ""), int(buf[i])) for i in range(min(n, 16))]
-
-
-def _call(ops, fn, *args):
-    """one C-ABI call on torch's current stream -> (return code, launch log), synchronised"""
-    L = ops._lib.lib()
-    rc = []
-    log = _logged(L, lambda: rc.append(fn(*args, ops._stream())))
-    torch.cuda.synchronize()
-    return rc[0], log
-
-
-def _ceil(a, b):
-    return -(-a // b)
+spell = functools.partial(spell, params=MACRO_PARAMS)
 
 
 def _round256(b):
     return (b + 255) & ~255
-
-
-def set_knobs(lib_option, knobs):
-    for k, v in knobs:
-        lib_option(k, v)
 
 
 def names(log):
@@ -391,11 +299,6 @@ def bounds(M, K, N, scale, ax=AMP):
     return (K * ax * AMP * scale + AMP, N * AMP * AMP * scale, M * AMP * ax * scale, M * AMP)
 
 
-def _below_2_24(*bs):
-    for b in bs:
-        assert int(b) < 2 ** 24, "a sum of this case can leave the exact range of fp32: bound %d" % int(b)
-
-
 def _ints(gen, *shape):
     return torch.randint(-AMP, AMP + 1, shape, generator=gen).to(F64)
 
@@ -447,19 +350,6 @@ def test_reference_is_the_oracle():
         for key, want in zip(("d_x", "d_w", "d_b"), knp.linear_act_bwd(x.numpy(), w.numpy(), y, gy.numpy(), a, None if m is None else m.numpy())):
             assert np.array_equal(res[key].numpy(), want), key
         assert float(res["d_x"].abs().max()) > 0 and (act == 0 or bool((res["y"] == 0).any()))
-
-
-def assert_exact(name, got, ref):
-    """got (fp32 GPU tensor) against the float64 integer reference, bit for bit (-0.0 counts as 0.0: an integer has one zero)"""
-    assert got.dtype == F32 and tuple(got.shape) == tuple(ref.shape), (name, got.dtype, tuple(got.shape), tuple(ref.shape))
-    assert bool((ref == ref.round()).all())
-    _below_2_24(int(ref.abs().max()))
-    have = got.detach().cpu().to(F64)
-    if not torch.equal(have, ref):           # (value equality: -0.0 == 0.0, NaN != anything)
-        bad = (have != ref).nonzero()
-        first = tuple(int(i) for i in bad[0])
-        raise AssertionError("%s: %d of %d elements differ from the integer reference; first at %s: got %r, want %r"
-                             % (name, len(bad), ref.numel(), first, float(have[first]), float(ref[first])))
 
 
 _masks = {}
@@ -892,19 +782,6 @@ def test_case_tables_reach_every_instantiation():
     assert want - seen == set(), "instantiations that no case launches"
 
 
-def launch_sites(path):
-    """the first argument of every VQA_LAUNCH( of a source file, blanks removed"""
-    text = open(path).read()
-    found = []
-    for m in re.finditer(r"\bVQA_LAUNCH\(", text):
-        depth, i = 0, m.end()
-        while depth or text[i] != ",":
-            depth += {"(": 1, ")": -1}.get(text[i], 0)
-            i += 1
-        found.append(re.sub(r"\s+", "", text[m.end():i]))
-    return found
-
-
 def test_every_launch_site_is_declared():
     """a launch site added to (or renamed in) one of the two files without a case here fails; so does a case whose site no longer exists"""
     per_file = [launch_sites(os.path.join(CSRC, f)) for f in K5_FILES]
@@ -917,29 +794,6 @@ def test_every_launch_site_is_declared():
 
 
 # ======================================================================================================================= B
-class Bars:
-    """kernel error against float64 over the tensor's largest magnitude; bar: four times the error of the same formulas in float32
-    with torch on the CPU, plus one float32 ulp.  Every figure is kept and reported through `measured`; close() fails if one missed
-    its bar (`fallback`: the bar the project already states for that output, where the first one is missed)."""
-
-    def __init__(self, measured, case):
-        self.measured, self.case, self.rows = measured, case, []
-
-    def check(self, name, got, ref64, ref32, fallback=None):
-        got = got.detach().cpu()
-        assert got.shape == ref64.shape and got.dtype == F32, (self.case, name, got.shape, ref64.shape)
-        mag = float(ref64.abs().max())
-        assert mag > 0.0, (self.case, name)
-        bar = 4.0 * float((ref32.double() - ref64).abs().max()) / mag + EPS32
-        err = float((got.double() - ref64).abs().max()) / mag if bool(torch.isfinite(got).all()) else float("inf")
-        self.rows.append((err, bar, name, fallback))
-        self.measured("%s %s" % (self.case, name), err, bar)
-
-    def close(self):
-        missed = [r for r in self.rows if not (r[0] <= r[1] or (r[3] is not None and r[0] <= r[3]))]
-        assert not missed, (self.case, [(n, "%.3e > %.3e" % (e, b)) for e, b, n, _ in missed])
-
-
 SPLIT_BAR = 2e-5      # tests/test_gpu_split.py's bar for the split engine
 # (id, entry, M | (B, Nr), K, N, act, p, knobs, forward form, forms that must be in the backward's log)
 RANDOM_CASES = [

@@ -9,17 +9,13 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_harness import dev
 from oracle import kernels_np as K
 from oracle import seeded
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 2e-4  # well inside the 1e-3 north-star tolerance
-
-
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
 
 
 def g(a, requires_grad=False):

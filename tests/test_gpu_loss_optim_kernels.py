@@ -10,16 +10,12 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_harness import dev
 from vqa_playground_pytorch_amd import metrics, ops
 
 pytestmark = pytest.mark.gpu
 
 BAR = 1e-5
-
-
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 # ---- the inputs and their float64 references, made once per shape -------------------------------------------------------------

@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from kernel_harness import dev
 from oracle import reference_faithful as RF
 from oracle import seeded
 
@@ -25,11 +26,6 @@ ZERO_GRADIENT = {
             | {"att%d.conv_att.conv.bias" % s for s in (1, 2)},
     "oda": {"att.conv_att.conv.bias"},
 }
-
-
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def build(cls, nans):

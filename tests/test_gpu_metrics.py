@@ -5,15 +5,11 @@ must be the same bits as the plain loss kernel's."""
 import pytest
 import torch
 
+from kernel_harness import dev
 from oracle import seeded
 from vqa_playground_pytorch_amd import metrics
 
 pytestmark = pytest.mark.gpu
-
-
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def case(B, C, seed, specials=True):

@@ -7,17 +7,13 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_harness import dev
 from oracle import reference_faithful as RF
 from oracle import seeded
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-3
-
-
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def rel(got, want):

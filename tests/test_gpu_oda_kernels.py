@@ -12,7 +12,7 @@ L and G) says that it was, and its result is compared whole.
      on the CPU, chunked over b.  Outputs sit in sentinel-filled buffers that are compared whole, inputs in NaN-padded ones, the
      workspace is exactly _bwd_workspace_bytes long, pre-filled with NaN, with a sentinel fence behind it.
   B  p = 0.25 (factor 4/3) with random operands against float64 (oracle/kernels_np.py, fed with the host mask), under the project's
-     bar (restated from tests/test_gpu_region_kernels.py): four times the error of the same formula in float32 with torch on the
+     bar (Bars of tests/kernel_harness.py): four times the error of the same formula in float32 with torch on the
      CPU plus one float32 ulp of the tensor's largest magnitude.  Every case reports what it measured.
   C  a NaN stays in its sample (what a dropped NaN becomes INSIDE its sample is not asserted: the bit layout ANDs it to 0, the byte
      layout multiplies it); refusals launch nothing and leave the outputs alone.  The forward accepts N = 40, L = 1024 (case
@@ -55,14 +55,11 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_harness import (E_BADARG, E_UNSUPPORTED, F32, NAN, PAD, Bars, _amax, _below_2_24, _call, _ceil, _in, _out, _ptr, _same_bits,
+                            _sentinel, _untouched, _win, assert_exact, dev, launch_sites, ops, set_knobs)  # noqa: F401  (ops: the fixture)
+
 gpu = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SENT = -12345.0
-E_BADARG, E_UNSUPPORTED = -1, -2
-EPS32 = float(torch.finfo(torch.float32).eps)
-F32 = torch.float32
-NAN = float("nan")
-PAD = 8                 # elements of sentinel (outputs) or NaN (inputs) in front of and behind every window: 32 bytes
 M32, M64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
 SALT = 0x1F00000007     # what a call that passes its seed through the device word adds on the host side
 
@@ -80,114 +77,6 @@ FUSED_T, FUSED_F = "(oda_bwd_fused_kernel<true>)", "(oda_bwd_fused_kernel<false>
 REDUCE, DBIAS = "oda_reduce_kernel", "oda_dbias_kernel<G>"
 FWD_MFMA_FORMS = (FWD_MFMA_PK, FWD_MFMA_T, FWD_MFMA_F)
 W_MFMA_FORMS = tuple(W_STAGED.values()) + (W_MFMA_PK, W_MFMA_T, W_MFMA_F)
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vqa_playground_pytorch_amd import _lib, ops as o
-    _lib.lib()
-    return o
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(_bits(a), _bits(b))
-
-
-def _ptr(t, off=0):
-    return ctypes.c_void_p(t.data_ptr() + t.element_size() * int(off)) if t is not None else None
-
-
-def _sentinel(*shape):
-    return torch.full(shape, SENT, device=dev(), dtype=F32)
-
-
-def _untouched(t):
-    return bool((_bits(t) == _bits(torch.full((1,), SENT, device=t.device, dtype=t.dtype))).all())
-
-
-def _take(buf, window, what):
-    """-> a copy of buf[window]; asserts that nothing else of the sentinel-filled `buf` changed"""
-    got = buf[window].clone()
-    buf[window] = SENT
-    assert _untouched(buf), "%s: a store outside the output window" % what
-    return got
-
-
-def _out(n):
-    """a sentinel-filled buffer with an n-element output window PAD elements in"""
-    buf = _sentinel(n + 2 * PAD)
-    assert buf.data_ptr() % 16 == 0
-    return buf
-
-
-def _win(buf, shape, what):
-    n = 1
-    for s in shape:
-        n *= s
-    return _take(buf, slice(PAD, PAD + n), what).view(*shape)
-
-
-def _in(t):
-    """CPU tensor (integers or fp32) -> an fp32 GPU buffer that holds it PAD elements in, NaN on both sides: a read outside the
-    window that is USED poisons an output"""
-    flat = t.reshape(-1).to(F32)
-    assert torch.equal(flat.to(torch.float64), t.reshape(-1).to(torch.float64)), "the operand is not exact in fp32"
-    buf = torch.full((flat.numel() + 2 * PAD,), NAN, dtype=F32)
-    buf[PAD:PAD + flat.numel()] = flat
-    return buf.to(dev())
-
-
-def _logged(L, call):
-    """run `call` -> [(kernel expression without blanks, grid in work-items)] of the launches it made"""
-    L.vqa_launch_log_reset()
-    call()
-    buf = (ctypes.c_ulonglong * 16)()
-    n = L.vqa_launch_log(buf, 16)
-    return [((L.vqa_launch_log_kernel(i) or b"").decode().replace(" ", ""), int(buf[i])) for i in range(min(n, 16))]
-
-
-def _call(ops, fn, *args):
-    """one C-ABI call on torch's current stream -> (return code, launch log), synchronised"""
-    L = ops._lib.lib()
-    rc = []
-    log = _logged(L, lambda: rc.append(fn(*args, ops._stream())))
-    torch.cuda.synchronize()
-    return rc[0], log
-
-
-def _amax(t):
-    return int(t.abs().max())
-
-
-def _below_2_24(*bounds):
-    for b in bounds:
-        assert int(b) < 2 ** 24, "a sum of this case can leave the exact range of fp32: bound %d" % int(b)
-
-
-def assert_exact(name, got, ref):
-    """got (fp32 GPU tensor) against the int64 reference, bit for bit (-0.0 folded into 0.0: an integer has one zero)"""
-    assert ref.dtype == torch.int64 and tuple(got.shape) == tuple(ref.shape), (name, got.dtype, tuple(got.shape), tuple(ref.shape))
-    assert got.dtype == F32, (name, got.dtype)
-    _below_2_24(_amax(ref))
-    want = ref.float()
-    have = got.detach().float().cpu() + 0.0
-    if not torch.equal(_bits(have), _bits(want)):
-        bad = (_bits(have) != _bits(want)).nonzero()
-        first = tuple(int(i) for i in bad[0])
-        raise AssertionError("%s: %d of %d elements differ from the integer reference; first at %s: got %r, want %r"
-                             % (name, len(bad), want.numel(), first, float(have[first]), float(want[first])))
-
-
-def _ceil(a, b):
-    return -(-a // b)
 
 
 # ======================================================================================================================= M: the host mask
@@ -465,11 +354,6 @@ def run_bwd(ops, dv, B, N, L, G, p, seed, via_word, gate):
     return rc, log, tuple(_win(o, sh, n) for o, sh, n in zip(outs, shapes, ("d_vl", "d_ql", "d_w", "d_bias")))
 
 
-def set_knobs(lib_option, knobs):
-    for k, v in knobs:
-        lib_option(k, v)
-
-
 NO_MFMA, NO_PK, BYTE_KNOB = ("VQA_K2_MFMA", 0), ("VQA_K2_PK", 0), ("VQA_K2_BYTE_MASK", 1)
 
 # (id, form, B, N, L, G, p, knobs)
@@ -623,29 +507,6 @@ def test_every_form_gives_the_same_bits(ops, lib_option):
 
 
 # ======================================================================================================================= B
-class Bars:
-    """kernel error against float64 over the tensor's largest magnitude; bar: four times the error of the same formulas in float32
-    with torch on the CPU, plus one float32 ulp.  Every figure is kept; close() reports the worst of the case through `measured`,
-    then fails if one missed its bar."""
-
-    def __init__(self, measured, case):
-        self.measured, self.case, self.rows = measured, case, []
-
-    def check(self, name, got, ref64, ref32):
-        got = got.detach().cpu()
-        assert got.shape == ref64.shape and got.dtype == F32, (self.case, name, got.shape, ref64.shape)
-        mag = float(ref64.abs().max())
-        assert mag > 0.0, (self.case, name)
-        bar = 4.0 * float((ref32.double() - ref64).abs().max()) / mag + EPS32
-        err = float((got.double() - ref64).abs().max()) / mag if bool(torch.isfinite(got).all()) else float("inf")
-        self.rows.append((err / bar, err, bar, name))
-        self.measured("%s %s" % (self.case, name), err, bar)
-
-    def close(self):
-        missed = [r for r in self.rows if not r[1] <= r[2]]
-        assert not missed, (self.case, [(n, "%.3e > %.3e" % (e, b)) for _, e, b, n in missed])
-
-
 def oda_f32(vl, ql, w, bias, mask, dS):
     """the formulas of oracle/kernels_np.py in float32 with torch on the CPU; mask [B,N,N,L]"""
     B, N, L = vl.shape
@@ -792,19 +653,6 @@ def declared_forms():
     """every kernel expression a case above names (and asserts from the launch log)"""
     forms = {s for table in (FWD_CASES, BWD_CASES, ISOLATION_CASES) for case in table for s in case if isinstance(s, str) and "_kernel" in s}
     return forms | {MASK_K, REDUCE, DBIAS}      # test_exported_mask_*; the last two launches of every backward case (bwd_log)
-
-
-def launch_sites(path):
-    """the first argument of every VQA_LAUNCH( of a source file, blanks removed"""
-    text = open(path).read()
-    found = []
-    for m in re.finditer(r"\bVQA_LAUNCH\(", text):
-        depth, i = 0, m.end()
-        while depth or text[i] != ",":
-            depth += {"(": 1, ")": -1}.get(text[i], 0)
-            i += 1
-        found.append(re.sub(r"\s+", "", text[m.end():i]))
-    return found
 
 
 def test_every_launch_site_is_declared():

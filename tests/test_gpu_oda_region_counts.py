@@ -1,6 +1,7 @@
 """Per-sample region counts for ODA: the masked object-difference kernels (csrc/object_difference_masked.hip,
 vqa_object_difference_attention_len_{fwd,bwd}) through the C ABI, one dispatch form at a time, and oda.Model(region_counts=True).
-The conventions are those of tests/test_gpu_oda_kernels.py, whose helpers are imported: outputs sit in sentinel-filled buffers that
+The conventions are those of tests/test_gpu_oda_kernels.py (tests/kernel_harness.py, and the unmasked file's own operands, host mask
+and calls, which are imported): outputs sit in sentinel-filled buffers that
 are compared whole, inputs in NaN-padded windows, the workspace is exactly _len_bwd_workspace_bytes long, NaN-filled, with a fence
 behind it, the launch log says which kernel ran, the mask is drawn on the host (host_keep).
 
@@ -36,10 +37,10 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_oda_kernels import (BYTE_KNOB, E_BADARG, E_UNSUPPORTED, F32, NAN, NO_MFMA, PAD, Bars, _amax, _below_2_24,
-                                  _call, _ceil, _out, _ptr, _same_bits, _sentinel, _untouched, _win, amplitude, assert_exact,
-                                  bounds, case_seed, dev, drop_cfg, host_keep, keep_factor, mfma_groups, nt_of, operands, run_bwd,
-                                  run_fwd, seed_args, set_knobs)
+from kernel_harness import (E_BADARG, E_UNSUPPORTED, F32, NAN, PAD, Bars, _amax, _below_2_24, _call, _ceil, _out, _ptr, _same_bits,
+                            _sentinel, _untouched, _win, assert_exact, dev, ops, set_knobs)  # noqa: F401  (ops: the fixture)
+from test_gpu_oda_kernels import (BYTE_KNOB, NO_MFMA, amplitude, bounds, case_seed, drop_cfg, host_keep, keep_factor, mfma_groups, nt_of,
+                                  operands, run_bwd, run_fwd, seed_args)
 
 pytestmark = pytest.mark.gpu
 
@@ -50,13 +51,6 @@ D_BYTE, D_PLAIN = "(oda_len_bwd_data_kernel<G,kLenByte>)", "(oda_len_bwd_data_ke
 W_MFMA_T, W_MFMA_F = "oda_len_bwd_weight_mfma_kernel<true>", "oda_len_bwd_weight_mfma_kernel<false>"
 W_BIT, W_BYTE, W_PLAIN = ("(oda_len_bwd_weight_kernel<G,kLen%s>)" % m for m in ("Bit", "Byte", "Plain"))
 REDUCE, DBIAS = "oda_len_reduce_kernel", "oda_len_dbias_kernel<G>"
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vqa_playground_pytorch_amd import _lib, ops as o
-    _lib.lib()
-    return o
 
 
 # ---- which kernels a call must launch, restated from the dispatch rules -----------------------------------------------------

@@ -2,7 +2,7 @@
 and 'v_len' through CoR2Model, the trainer's captured step and the evaluator's replayed forward.
 
   A  kernels against float64: the reference is oracle/kernels_np.py's K3 applied per sample to the rows n < len_b, zeros filled in
-     beyond; bar as tests/test_gpu_region_kernels.py derives it (Bars: four times the error of the same formulas in float32 on the
+     beyond; bar as tests/test_gpu_region_kernels.py reports it (Bars: four times the error of the same formulas in float32 on the
      CPU plus one ulp; 2^-8 |ref| on top for a bf16 d_v; an exactly-zero reference asks for exactly zero).  The padded rows of the
      INPUTS hold large finite values (sample 0's first padded logit +80): a kernel that reads one fails every bar.
   B  full length equals the unmasked entry points (forward bit for bit), the masked backward is reproducible bit for bit.
@@ -16,8 +16,9 @@ import torch
 
 from oracle import reference_faithful as RF
 from oracle import seeded
-from test_gpu_region_kernels import (BF, E_BADARG, E_UNSUPPORTED, F32, PAD, Bars, _call, _ceil, _dp64, _dt_id, _out, _ptr, _sentinel,
-                                     _sfx, _untouched, _win, dev, k3_mask)
+from kernel_harness import (BF, E_BADARG, E_UNSUPPORTED, F32, PAD, _call, _ceil, _out, _ptr, _sentinel, _untouched, _win, dev,
+                            ops)  # noqa: F401  (ops: the fixture)
+from test_gpu_region_kernels import Bars, _dp64, _dt_id, _sfx, k3_mask
 
 pytestmark = pytest.mark.gpu
 
@@ -27,13 +28,6 @@ K3L_ROWS, K3L_SOFTMAX = "(attention_pool_len_bwd_kernel<T,NT,G,false>)", "attent
 K3L_WHOLE = "(attention_pool_len_bwd_kernel<T,NT,G,true>)"
 ROWS = 16               # region rows per workgroup of the two-launch backward's first kernel
 WHOLE_MIN_B = "VQA_K3_LEN_WHOLE_MIN_B"      # the batch from which the backward is one launch, one workgroup per sample (default 256)
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vqa_playground_pytorch_amd import _lib, ops as o
-    _lib.lib()
-    return o
 
 
 def _lens_of(N):

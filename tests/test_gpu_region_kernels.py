@@ -8,9 +8,10 @@ log (kernel expression and grid in work-items) says that it was, and its result 
      CPU (mode 0 by the closed form q1 sum_i a_i v_i + (sum a) q2 v_j, exact over integers); fp32 outputs equal it bit for bit (-0 is
      0), bf16 outputs equal ref.float().to(bfloat16) bit for bit.  Outputs sit in sentinel-filled buffers that are compared whole;
      alpha is read as glimpse 1 of a [B,N,3] tensor (alpha_stride = 3); D leaves the last column block partial.
-  B  K3 with random operands against float64 (oracle/kernels_np.py), under the project's bar (restated from
-     tests/test_gpu_encoder_bf16.py): four times the error of the same formula in float32 with torch on the CPU plus one float32 ulp
-     of the tensor's largest magnitude; a bf16 d_v gets 2^-8 |ref| on top.  Every case reports what it measured.
+  B  K3 with random operands against float64 (oracle/kernels_np.py), under the project's bar (Bars of
+     tests/kernel_harness.py, reported here as one row per case): four times the error of the same formula in float32 with torch
+     on the CPU plus one float32 ulp of the tensor's largest magnitude; a bf16 d_v gets 2^-8 |ref| on top.  Every case reports
+     what it measured.
   C  non-finite isolation and refusals of K3.
   D  test_every_launch_site_is_declared (no GPU): every VQA_LAUNCH first argument of the two files is the form of some case below.
 
@@ -39,20 +40,16 @@ Dispatch form (as the launch log spells it) -> the test that launches it and ass
 import ctypes
 import functools
 import os
-import re
 
 import pytest
 import torch
 
+import kernel_harness
+from kernel_harness import (BF, EPS32, E_BADARG, E_UNSUPPORTED, F32, INF, NAN, PAD, _amax, _below_2_24, _call, _ceil, _d, _out, _ptr,
+                            _same_bits, _sentinel, _untouched, _win, assert_exact, dev, launch_sites, ops)  # noqa: F401  (ops: the fixture)
+
 gpu = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SENT = -12345.0
-E_BADARG, E_UNSUPPORTED = -1, -2
-EPS32 = float(torch.finfo(torch.float32).eps)
-EPS_BF16 = 2.0 ** -8
-F32, BF = torch.float32, torch.bfloat16
-NAN = float("nan")
-PAD = 8                 # elements of sentinel in front of and behind every output window (32 bytes fp32, 16 bytes bf16)
 AG, GL = 3, 1           # alpha is glimpse GL of a [B,N,AG] tensor: alpha_stride = AG
 _dt_id = lambda dt: "bf16" if dt == BF else "f32"      # noqa: E731
 
@@ -70,121 +67,12 @@ K3_STREAM4, K3_STREAM1 = "(attention_pool_bwd_stream_kernel<T,NT,G,RS>)", "(atte
 K3_SOFTMAX = "attention_softmax_bwd_kernel"
 
 
-def dev():
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vqa_playground_pytorch_amd import _lib, ops as o
-    _lib.lib()
-    return o
-
-
 def _sfx(dt):
     return "_bf16" if dt == BF else ""
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int16 if t.dtype == BF else torch.int32)
-
-
-def _same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(_bits(a), _bits(b))
-
-
-def _ptr(t, off=0):
-    return ctypes.c_void_p(t.data_ptr() + t.element_size() * int(off)) if t is not None else None
-
-
-def _sentinel(*shape, dtype=F32):
-    return torch.full(shape, SENT, device=dev(), dtype=dtype)
-
-
-def _untouched(t):
-    return bool((_bits(t) == _bits(torch.full((1,), SENT, device=t.device, dtype=t.dtype))).all())
-
-
-def _take(buf, window, what):
-    """-> a copy of buf[window]; asserts that nothing else of the sentinel-filled `buf` changed"""
-    got = buf[window].clone()
-    buf[window] = SENT
-    assert _untouched(buf), "%s: a store outside the output window" % what
-    return got
-
-
-def _out(n, dtype=F32):
-    """a sentinel-filled buffer with an n-element output window PAD elements in"""
-    buf = _sentinel(n + 2 * PAD, dtype=dtype)
-    assert buf.data_ptr() % 16 == 0
-    return buf
-
-
-def _win(buf, shape, what):
-    n = 1
-    for s in shape:
-        n *= s
-    return _take(buf, slice(PAD, PAD + n), what).view(*shape)
-
-
-def _logged(L, call):
-    """run `call` -> [(kernel expression without blanks, grid in work-items)] of the launches it made"""
-    L.vqa_launch_log_reset()
-    call()
-    buf = (ctypes.c_ulonglong * 16)()
-    n = L.vqa_launch_log(buf, 16)
-    return [((L.vqa_launch_log_kernel(i) or b"").decode().replace(" ", ""), int(buf[i])) for i in range(min(n, 16))]
-
-
-def _call(ops, fn, *args):
-    """one C-ABI call on torch's current stream -> (return code, launch log), synchronised"""
-    L = ops._lib.lib()
-    rc = []
-    log = _logged(L, lambda: rc.append(fn(*args, ops._stream())))
-    torch.cuda.synchronize()
-    return rc[0], log
-
-
 def _ints(gen, *shape, amp=4):
     return torch.randint(-amp, amp + 1, shape, generator=gen)
-
-
-def _d(t, dt):
-    """CPU integer tensor -> dt on the GPU, exactly"""
-    out = t.to(F32).to(dt)
-    assert torch.equal(out.to(torch.float64), t.to(torch.float64)), "the operand is not exact in %s" % dt
-    return out.to(dev()).contiguous()
-
-
-def _amax(t):
-    return int(t.abs().max())
-
-
-def _below_2_24(*bounds):
-    for b in bounds:
-        assert int(b) < 2 ** 24, "a sum of this case can leave the exact range of fp32: bound %d" % int(b)
-
-
-def assert_exact(name, got, ref):
-    """got (fp32 or bf16 GPU tensor) against the int64 reference: fp32 bit for bit (-0.0 folded into 0.0: an integer has one zero),
-    bf16 == ref.float().to(bf16) bit for bit"""
-    assert ref.dtype == torch.int64 and tuple(got.shape) == tuple(ref.shape), (name, got.dtype, tuple(got.shape), tuple(ref.shape))
-    _below_2_24(_amax(ref))
-    want = ref.float()
-    if got.dtype == BF:
-        want = want.to(BF).float()
-    else:
-        assert got.dtype == F32, (name, got.dtype)
-    have = got.detach().float().cpu() + 0.0
-    if not torch.equal(_bits(have), _bits(want)):
-        bad = (_bits(have) != _bits(want)).nonzero()
-        first = tuple(int(i) for i in bad[0])
-        raise AssertionError("%s: %d of %d elements differ from the integer reference; first at %s: got %r, want %r"
-                             % (name, len(bad), want.numel(), first, float(have[first]), float(want[first])))
-
-
-def _ceil(a, b):
-    return -(-a // b)
 
 
 # ======================================================================================================================= A: K1 forward
@@ -462,37 +350,17 @@ def test_relation_apply_backward_threshold(ops):
 
 
 # ======================================================================================================================= B: K3
-class Bars:
-    """kernel error against float64 over the tensor's largest magnitude; bar: four times the error of the same formulas in float32
-    with torch on the CPU, plus one float32 ulp.  A bf16 result: elementwise within 2^-8 |ref| + that bar x the magnitude.
-    Every figure is kept; close() reports the worst of the case through `measured`, then fails if one missed its bar."""
+class Bars(kernel_harness.Bars):
+    """kernel_harness.Bars with one row per case instead of one per check(): close() hands the worst of the case, by err / bar, to
+    `measured`, then fails if one missed its bar"""
 
-    def __init__(self, measured, case):
-        self.measured, self.case, self.rows = measured, case, []
-
-    def check(self, name, got, ref64, ref32):
-        got = got.detach().cpu()
-        assert got.shape == ref64.shape, (self.case, name, got.shape, ref64.shape)
-        mag = float(ref64.abs().max())
-        if mag == 0.0:      # (N = 1: d_logits = alpha (dal - alpha dal) is 0 in every precision) no scale, no allowance: exactly 0
-            assert not bool(ref32.any()), (self.case, name)
-            err = float(got.double().abs().max())
-            self.rows.append((0.0 if err == 0.0 else float("inf"), err, 0.0, name))
-            return
-        bar = 4.0 * float((ref32.double() - ref64).abs().max()) / mag + EPS32
-        diff = (got.double() - ref64).abs()
-        if got.dtype == BF:
-            diff = (diff - EPS_BF16 * ref64.abs()).clamp_min(0.0)
-        else:
-            assert got.dtype == F32, (self.case, name, got.dtype)
-        err = float(diff.max()) / mag if bool(torch.isfinite(got.float()).all()) else float("inf")
-        self.rows.append((err / bar, err, bar, name))
+    def report(self, name, err, bar):
+        pass
 
     def close(self):
-        ratio, err, bar, name = max(self.rows)
+        _, err, bar, name = max((err / bar if bar else (INF if err else 0.0), err, bar, name) for err, bar, name, _ in self.rows)
         self.measured(self.case, err, bar, name)
-        missed = [r for r in self.rows if not r[1] <= r[2]]
-        assert not missed, (self.case, [(n, "%.3e > %.3e" % (e, b)) for _, e, b, n in missed])
+        super().close()
 
 
 def k3_mask(ops, B, G, D, p, seed):
@@ -785,19 +653,6 @@ def declared_forms():
     forms |= {K1_BWD[dual, form] for _, form, *_ in K1_BWD_CASES + [("threshold", "RS")] for dual in (False, True)}
     forms.add(K3_SOFTMAX)            # the third launch of every K3_STREAM4 / K3_STREAM1 case (k3_bwd_log)
     return forms
-
-
-def launch_sites(path):
-    """the first argument of every VQA_LAUNCH( of a source file, blanks removed"""
-    text = open(path).read()
-    found = []
-    for m in re.finditer(r"\bVQA_LAUNCH\(", text):
-        depth, i = 0, m.end()
-        while depth or text[i] != ",":
-            depth += {"(": 1, ")": -1}.get(text[i], 0)
-            i += 1
-        found.append(re.sub(r"\s+", "", text[m.end():i]))
-    return found
 
 
 def test_every_launch_site_is_declared():

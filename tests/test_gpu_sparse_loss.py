@@ -17,16 +17,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from kernel_harness import dev
 from vqa_playground_pytorch_amd import _lib, metrics, ops
 
 pytestmark = pytest.mark.gpu
 
 BAR = 1e-5
-
-
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def reference_dense(a_idx, a_val, C):

@@ -12,21 +12,11 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_harness import dev, ops  # noqa: F401  (ops: the fixture)
 from oracle import kernels_np as K
 from oracle import seeded
 
 pytestmark = pytest.mark.gpu
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vqa_playground_pytorch_amd import _lib, ops as o
-    _lib.lib()
-    return o
 
 
 def err(got, ref):

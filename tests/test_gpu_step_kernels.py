@@ -48,6 +48,7 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_harness import dev
 from vqa_playground_pytorch_amd import _lib, ops
 
 pytestmark = pytest.mark.gpu
@@ -56,11 +57,6 @@ F32 = np.float32
 SENT = 2.0 ** 25                 # exact in fp32 and bf16; one of them in a sum of |entries| <= 8 cannot go unseen
 LR, B1, B2, EPS = 1e-3, 0.9, 0.999, 1e-8
 SIZES = [1, 3, 4, 5, 1023, 1024, 1025, 4099, 2 ** 20 + 3]        # as tests/test_gpu_loss_optim_kernels.py
-
-
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def ptr(t):
