@@ -7,14 +7,13 @@ being the literal 36, and per-replica batch 1 works (the reference raises IndexE
 import os
 
 import torch
-import torch.nn as nn
 
 from . import head, ops
-from .layers import MutanFusion, MyATT, MyConv1d, MyLinear, QuestionVectorInput, SideOutputs, linear_stack_groups, my_linears, \
-    question_feature
+from .layers import MutanFusion, MyATT, MyConv1d, MyLinear, RegionQuestionModel, SideOutputs, _rate, _seed, linear_stack_groups, \
+    my_linears, question_feature
 
 
-class Model(nn.Module):
+class Model(RegionQuestionModel):
     def __init__(self, vocab_words=None, num_ans=None, seq2vec=None, relation_mode=1, compute_dtype=None, encoder_dtype=None,
                  encoder_input_dtype=None):
         super().__init__()
@@ -31,19 +30,7 @@ class Model(nn.Module):
         # 0 = pairwise (every (i,j) term summed from the LDS tile), 1 = factored (same value, one pass)
         self.relation_mode = relation_mode
 
-        if seq2vec == "skipthoughts":      # the reference's encoder (config/CoR2.py:166), randomly initialised here
-            from .encoder import SkipThoughts, encoder_dtype_from, encoder_input_dtype_from
-            seq2vec = SkipThoughts(vocab_list=vocab_words, gru="BayesianGRU", return_last=True, af="relu",
-                                   compute_dtype=encoder_dtype_from(encoder_dtype),
-                                   input_dtype=encoder_input_dtype_from(encoder_input_dtype))
-        elif encoder_dtype is not None or encoder_input_dtype is not None:
-            given = seq2vec if seq2vec is None or isinstance(seq2vec, str) else type(seq2vec).__name__
-            raise ValueError("%s configures the SkipThoughts encoder that seq2vec='skipthoughts' builds; "
-                             "it cannot be given with seq2vec=%r"
-                             % ("encoder_dtype" if encoder_dtype is not None else "encoder_input_dtype", given))
-        if seq2vec == "vector":             # explicit pass-through slot: sample['q_idxes'] holds the 2400-d question vector
-            seq2vec = None
-        self.seq2vec = seq2vec if seq2vec is not None else QuestionVectorInput(2400)
+        self._set_seq2vec(seq2vec, vocab_words, encoder_dtype, encoder_input_dtype)
         self.compress_v = MyConv1d(2048, 310, 1, 1, p=0.5, af="relu")
         self.compress_v2 = MyConv1d(2048, 310, 1, 1, p=0.5, af="relu")
         self.compress_q = MyLinear(2400, 310, p=0.5, af="relu")
@@ -112,13 +99,6 @@ class Model(nn.Module):
         mods = [self.compress_v2, self.fusion_vq2, self.att2, self.fusion_final, self.linear_classif]
         return [p for m in mods for p in m.parameters()]
 
-    def forward_with_cut(self, sample):
-        """-> (logits, outs, ins): ``outs`` are the first reasoning step's results that the second one reads, ``ins`` the
-        detached aliases it actually consumed.  d loss / d ins fed as grad_outputs of ``outs`` completes the backward."""
-        cut = []
-        logits = self(sample, cut)
-        return logits, cut[0], cut[1]
-
     def stack_groups(self):
         return linear_stack_groups([self.compress_q, self.linear_q, self.compress_q_1, self.compress_q_2]) + \
             linear_stack_groups([self.expand_q_1, self.expand_q_2])
@@ -152,10 +132,8 @@ class Model(nn.Module):
         sigmoid gates and the question-side rank factors of all three Mutan fusions.
         -> (q_gate_1, q_gate_2, h2 of fusion_vq1, of fusion_vq2, of fusion_final)."""
         proj = [self.compress_q, self.linear_q, self.compress_q_1, self.compress_q_2]
-        p_in = float(proj[0].p) if (self.training and proj[0].p) else 0.0
-        p_g = float(self.expand_q_1.p) if (self.training and self.expand_q_1.p) else 0.0
-        lows = head.QuestionProjections.apply(q_feature.contiguous(), p_in, ops.next_dropout_seed() if p_in else 0, (2, 3), p_g,
-                                              ops.next_dropout_seed() if p_g else 0, (),
+        p_in, p_g = _rate(proj[0]), _rate(self.expand_q_1)
+        lows = head.QuestionProjections.apply(q_feature.contiguous(), p_in, _seed(p_in), (2, 3), p_g, _seed(p_g), (),
                                               *[m.linear.weight for m in proj], *[m.linear.bias for m in proj])
         s = 1.0 / (1.0 - p_g) if p_g else 1.0
         fus = [self.fusion_vq1, self.fusion_vq2, self.fusion_final]
@@ -166,16 +144,6 @@ class Model(nn.Module):
         return head.GatesAndRankFactors.apply(4, (2, 3), ((0, fus[0].R), (0, fus[1].R), (1, fus[2].R)), (1.0, 1.0, s, s),
                                               *lows, *params)
 
-    def _final_phases(self, v1_att, v2_att, h2_final):
-        """Phases 5 and 6: fusion_final (its first input is cat(v1_att, v2_att), never materialised) with the rank product and
-        the classifier's input dropout in its epilogue, then the classifier."""
-        p_c = float(self.linear_classif.p) if (self.training and self.linear_classif.p) else 0.0
-        seed = ops.next_dropout_seed() if p_c else 0
-        lins = list(self.fusion_final.list_linear1)
-        x = head.VectorFusion.apply(h2_final, p_c, seed, 2, v1_att, v2_att, *[l.linear.weight for l in lins],
-                                    *[l.linear.bias for l in lins])
-        return head.Classifier.apply(x, self.linear_classif.linear.weight, self.linear_classif.linear.bias, p_c, seed)
-
     def relation_reduce(self, v_feature, q_gate_1, q_gate_2, alpha):
         """config/CoR2.py:191-199 (decare_cat) + :216 fused: v2[b,j] = sum_i alpha[b,i,0] *
         (v[b,i]*q1[b] + v[b,j]*q2[b]); the [B,N,N,D] tensor is never built (HIP kernel K1)."""
@@ -183,24 +151,11 @@ class Model(nn.Module):
                                             mode=self.relation_mode, dual=True)
 
     def forward(self, sample, _cut=None):
-        v = sample["v"]
-        b = v.size(0)
-        v_feature = v.contiguous().view(b, -1, 2048)
-        # 'v_len' (optional): the number of real regions of every sample, the rest of its N rows being (finite) padding.
-        # Both attentions mask their softmax with it (K3 `_len_` kernels): alpha is exactly 0 on the padding, so the padded
-        # rows reach neither the pooled features, nor the relation step (alpha1[..., 0]), nor any gradient.
-        v_len = sample.get("v_len")
-        if v_len is not None:
-            if v_len.dim() != 1 or v_len.size(0) != b:
-                raise ValueError("v_len must be [B] = [%d], got %s" % (b, tuple(v_len.shape)))
-            v_len = ops.region_counts(v_len, v_feature.size(1), v_feature.device)
+        # 'v_len' (optional): both attentions mask their softmax with it (K3 `_len_` kernels): alpha is exactly 0 on the padding,
+        # so the padded rows reach neither the pooled features, nor the relation step (alpha1[..., 0]), nor any gradient.
+        v_feature, v_len = self._region_input(sample)
         if v_feature.dtype != self.compute_dtype:
-            # bf16 regions into the fp32 path: the feed's transport format (feed.store_batches(region_dtype=torch.bfloat16): half
-            # the host -> device bytes), widened exactly by one HIP pass; everything downstream is the fp32 step
-            if v_feature.is_cuda and v_feature.dtype == torch.bfloat16 and self.compute_dtype == torch.float32:
-                v_feature = ops.widen_bf16(v_feature)
-            else:
-                v_feature = v_feature.to(self.compute_dtype)
+            v_feature = v_feature.to(self.compute_dtype)
         q_feature = question_feature(self.seq2vec, sample["q_idxes"] if "q_idxes" in sample else sample["q"])
 
         shad = self._bf16_shadows() if v_feature.dtype == torch.bfloat16 and v_feature.is_cuda else {}
@@ -217,19 +172,12 @@ class Model(nn.Module):
                                                                 return_pooled=True, grouped=grouped, lens=v_len)
         if _cut is not None:
             # everything the second reasoning step (relation, compress_v2, fusion_vq2, att2, fusion_final, classifier)
-            # reads from the first.  The second step runs on detached aliases of these tensors, so a backward pass from the
-            # loss ends at the aliases (some of the originals are ancestors of others -- q_feature_low of v1_att -- and
-            # would otherwise drag the first step's layers into it); a second pass then carries the aliases' gradients
-            # from the originals to the inputs (see late_parameters / trainer.DataParallelTrainer overlap)
-            outs = [q_feature_low, q_final, q_gate_1, q_gate_2, pooled1_first, v1_att, alpha1_full]
-            ins = [t.detach().requires_grad_(t.requires_grad) for t in outs]
-            _cut.extend([outs, ins])
-            q_feature_low, q_final, q_gate_1, q_gate_2, pooled1_first, v1_att, alpha1_full = ins
+            # reads from the first (q_feature_low is an ancestor of v1_att: see _cut_aliases, late_parameters)
+            q_feature_low, q_final, q_gate_1, q_gate_2, pooled1_first, v1_att, alpha1_full = self._cut_aliases(
+                _cut, [q_feature_low, q_final, q_gate_1, q_gate_2, pooled1_first, v1_att, alpha1_full])
 
         cv2 = self.compress_v2
-        w2 = cv2.conv.weight.squeeze(-1)
-        fused_node = cv2.af == "relu" and cv2.fused and b * v_feature.size(1) >= 1024 and v_feature.dtype == torch.float32 and \
-            ops.relation_projection_supported(v_feature, w2)
+        fused_node = cv2.relation_projection_ok(v_feature)
         if self.relation_mode == 1 or (fused_node and ops.pairwise_projection_supported(v_feature)):
             # Closed form of the relation step (config/CoR2.py:191-199 + :216).  Only glimpse 0 of alpha1 weights it, and
             # sum_i alpha1[i,0] v_i is exactly glimpse 0 of the pooled features att1 has just produced, while a softmax
@@ -244,7 +192,7 @@ class Model(nn.Module):
             else:
                 t = t_b = q_gate_1 * pooled1_first
                 c2 = c2_b = q_gate_2
-            p = self.compress_v2.p if (self.training and self.compress_v2.p) else 0.0
+            p = _rate(cv2)
             if fused_node:
                 # relation step + projection as one autograd node: backward reduces the projection's data gradient to
                 # d_t / d_c2 inside the GEMM tile (csrc/relation_dgrad.hip) instead of writing and re-reading [B,N,2048].
@@ -252,16 +200,15 @@ class Model(nn.Module):
                 # the reference's structure); everything else -- the backward through (t, c2), the second attention pooling v
                 # itself -- is shared with the closed form, which it equals.
                 pairwise = (q_gate_1, q_gate_2, alpha1_full, 0) if self.relation_mode != 1 else None
-                v2_feature_low = ops.relation_projection(v_feature, t, c2, w2, cv2.conv.bias, p,
-                                                         ops.next_dropout_seed() if p else 0, cv2.grad_pregated, pairwise)
+                v2_feature_low = ops.relation_projection(v_feature, t, c2, cv2.conv.weight.squeeze(-1), cv2.conv.bias, p,
+                                                         _seed(p), cv2.grad_pregated, pairwise)
             else:
-                v2_dropped = ops.relation_apply(v_feature, t, c2, p, ops.next_dropout_seed() if p else 0)
+                v2_dropped = ops.relation_apply(v_feature, t, c2, p, _seed(p))
                 v2_feature_low = cv2(v2_dropped, predropped=True, packed=shad.get("compress_v2"))
             fuse2 = self.fusion_vq2(v2_feature_low, q_feature_low, relu_input=self.compress_v2.grad_pregated,
                                     packed=shad.get("fusion_vq2"), h2=h2_2)
             v2_att, alpha2, _ = self.att2.attend(v_feature, self.att2.conv_att.pre_activation(fuse2),
-                                                 lambda pooled, pd: ops.relation_apply(
-                                                     pooled, t_b, c2_b, pd, ops.next_dropout_seed() if pd else 0),
+                                                 lambda pooled, pd: ops.relation_apply(pooled, t_b, c2_b, pd, _seed(pd)),
                                                  grouped=grouped, lens=v_len)
             # the reference's v2_feature[:, [0, 1], :] (visu.py:198-207 reads it after an eval forward).  Eval: computed here,
             # like the reference does.  Training: a step never looks at it, so it is computed when read, from copies of the
@@ -292,7 +239,7 @@ class Model(nn.Module):
                                        "feature": feature})
 
         if grouped:
-            return self._final_phases(v1_att, v2_att, h2_final)
+            return self._grouped_tail(h2_final, v1_att, v2_att)
         v_f = torch.cat([v1_att, v2_att], dim=1)
         x = self.fusion_final(v_f, q_final)
         return self.linear_classif(x)

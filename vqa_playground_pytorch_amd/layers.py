@@ -16,13 +16,14 @@ On GPU tensors every layer takes the HIP path and raises if the library is missi
 expressions in this file (bmul, bmatmul, _activation, the non-CUDA branches) exist for CPU tensors
 only -- shape checks and the state_dict tests -- and are never part of a measured step.
 """
+import collections
 import os
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import head, ops
 
 
 def bmul(inputs1, inputs2):
@@ -50,6 +51,30 @@ def _activation(x, af, dim):
     return getattr(F, af)(x)
 
 
+# How MyConv1d serves one call (MyConv1d._route): form = the op ("logits": K3a ops.attention_logits, "k5": ops.linear_act,
+# "bf16_engine": ops.linear_bf16, "bf16_library" / "library": ops.linear on packed bf16 / the fp32 operands), act = the
+# activation inside that op, drop = the rate of a torch dropout pass in front of it, p = the rate of the mask inside the
+# kernel, post = the torch activation applied to its result.
+_Route = collections.namedtuple("_Route", "form act drop p post")
+
+
+def _rate(module):
+    """The module's input dropout rate in its current mode: its ``p`` while training, 0.0 in eval or without dropout."""
+    p = getattr(module, "p", None)
+    return float(p) if (p and module.training) else 0.0
+
+
+def _seed(p):
+    """A dropout seed for a kernel that masks at rate p, drawn from torch's CPU generator (so torch.manual_seed governs the
+    mask) -- only when there is a mask to draw: at rate 0 nothing is consumed."""
+    return ops.next_dropout_seed() if p else 0
+
+
+def _last_dim_error(in_features, out_features, got):
+    return ValueError("[error] putils.Linear(%s, %s): last dimension of input(%s) should equal to in_features(%s)"
+                      % (in_features, out_features, got, in_features))
+
+
 def _same_config(mods, keys):
     first = mods[0]
     return all(all(getattr(m, k) == getattr(first, k) for k in keys) for m in mods)
@@ -75,11 +100,9 @@ def my_linears(mods, x, group_first=False, predropped=False):
         outs = [m(x if x.dim() == 2 else x[:, g, :]) for g, m in enumerate(mods)]
         return torch.stack(outs, 0 if group_first else 1)
     if x.size(-1) != first.in_features:
-        raise ValueError(
-            "[error] putils.Linear(%s, %s): last dimension of input(%s) should equal to in_features(%s)"
-            % (first.in_features, first.out_features, x.size(-1), first.in_features))
-    training = getattr(first, "training", False)
-    if x.dim() == 2 and not group_first and not (p and training) and af in (None, "") and x.dtype == torch.float32:
+        raise _last_dim_error(first.in_features, first.out_features, x.size(-1))
+    rate = _rate(first)
+    if x.dim() == 2 and not group_first and not rate and af in (None, "") and x.dtype == torch.float32:
         # G layers on ONE input without dropout or activation (Mutan's rank factors, putils/__init__.py:232-238): a
         # plain GEMM against the [G*A, K] stack -- the sum over the groups in the data gradient happens inside the GEMM
         # (no expand / reduce pair around a batched one), the bias gradient is one column sum
@@ -90,7 +113,7 @@ def my_linears(mods, x, group_first=False, predropped=False):
                 b = ops.stack_params([l.bias for l in lins]).reshape(G * first.out_features)
             y = ops.linear(x, w.view(G * first.out_features, first.in_features), b)
             return y.view(x.size(0), G, first.out_features)
-    drop = bool(p) and training and not predropped
+    drop = bool(rate) and not predropped
     if x.dim() == 2 and drop and x.dtype == torch.float32:
         x = ops.dropout(x, p, groups=G).transpose(0, 1)              # G independent draws over the one input: [B,G,K] view
         drop = False
@@ -134,9 +157,7 @@ class Linear(nn.Module):
 
     def forward(self, x):
         if x.size()[-1] != self.in_features:
-            raise ValueError(
-                "[error] putils.Linear(%s, %s): last dimension of input(%s) should equal to in_features(%s)"
-                % (self.in_features, self.out_features, x.size(-1), self.in_features))
+            raise _last_dim_error(self.in_features, self.out_features, x.size(-1))
         return ops.linear(x, self.linear.weight, self.linear.bias)
 
 
@@ -156,11 +177,10 @@ class MyLinear(nn.Module):
 
     def forward(self, x):
         if x.size()[-1] != self.in_features:
-            raise ValueError(
-                "[error] putils.Linear(%s, %s): last dimension of input(%s) should equal to in_features(%s)"
-                % (self.in_features, self.out_features, x.size(-1), self.in_features))
-        if self.p and self.training:
-            x = ops.dropout(x, self.p) if (x.is_cuda and x.dtype == torch.float32) else F.dropout(x, p=self.p, training=True)
+            raise _last_dim_error(self.in_features, self.out_features, x.size(-1))
+        p = _rate(self)
+        if p:
+            x = ops.dropout(x, p) if (x.is_cuda and x.dtype == torch.float32) else F.dropout(x, p=p, training=True)
         return _activation(ops.linear(x, self.linear.weight, self.linear.bias), self.af, self.dim)
 
 
@@ -188,46 +208,6 @@ class MyConv1d(nn.Module):
 
     # bf16 path: "engine" = the hand-written bf16 MFMA GEMMs (ops.LinearBf16), "library" = hipBLASLt through F.linear
     bf16_gemm = os.environ.get("VQA_BF16_GEMM", "engine")
-
-    def _linear_bf16(self, x, af, p=0.0, packed=None):
-        """Mixed-precision form (x bf16, last dim possibly zero-padded past in_channels): bf16 operands, fp32
-        accumulate, fp32 master weights.  Wide layers return the output padded to a multiple of 64 (pad = 0) so the
-        next bf16 GEMM needs no tail; narrow ones (the G attention logits) come back as fp32.  p: this layer's input
-        dropout rate in the current mode (0 in eval / when the producer dropped x already); at 0.5 it runs inside the GEMM
-        kernels (ops.LinearBf16).  packed: the layer's shadows from the model's ShadowPlan, or None."""
-        w = self.conv.weight.squeeze(-1)
-        if self.out_channels >= 32 and self.bf16_gemm == "engine" and af in (None, "", "relu"):
-            if p and (p != 0.5 or x.requires_grad):
-                # the in-kernel mask exists at p = 0.5 and has no data gradient (compress_v reads the model input); an x
-                # that needs one (compress_v2 behind the pairwise relation, relation_mode=0) is dropped beforehand
-                x, p = F.dropout(x, p=p, training=True), 0.0
-            return ops.linear_bf16(x, w, self.conv.bias, af, p, ops.next_dropout_seed() if p else 0,
-                                   pregated=self.grad_pregated, packed=packed)
-        if p:
-            x = F.dropout(x, p=p, training=True)
-        n_p = ops.pad_to(self.out_channels) if self.out_channels >= 32 else self.out_channels
-        wp = ops.PackedWeightBf16.apply(w, n_p, x.size(-1))
-        bp = F.pad(self.conv.bias, (0, n_p - self.out_channels)).to(torch.bfloat16)
-        y = ops.linear(x, wp, bp)
-        if self.out_channels < 32:
-            return _activation(y.float(), af, self.dim)
-        return _activation(y, af, self.dim)
-
-    def pre_activation(self, x):
-        if x.dim() != 3:
-            raise ValueError("[error] putils.Conv1d(%s, %s, %s, %s): input_dim (%s) should equal to 3"
-                             % (self.in_channels, self.out_channels, self.kernel_size, self.stride, x.dim()))
-        if ops.attention_logits_supported(x, self.in_channels, self.out_channels):
-            # the G attention logits of MyATT: dropout + 1x1 conv in one HIP kernel (K3a), fp32 out for either storage
-            p = self.p if (self.training and self.p) else 0.0
-            return ops.attention_logits(x, self.conv.weight.squeeze(-1), self.conv.bias, p,
-                                        ops.next_dropout_seed() if p else 0)
-        if x.dtype == torch.bfloat16:
-            return self._linear_bf16(x, None, self.p if (self.training and self.p) else 0.0)
-        if self.p:
-            x = F.dropout(x, p=self.p, training=self.training)
-        return ops.linear(x, self.conv.weight.squeeze(-1), self.conv.bias)
-
     # K5 (fused dropout+GEMM+bias+relu on the hand-written fp32 MFMA engines) vs the library GEMM + a separate dropout
     # pass: set per process with VQA_FUSED_LINEAR=0/1.  Default: fused -- since the register-tile engine
     # (csrc/gemm_f32_rt.hpp) the forward beats the library GEMM at these shapes and no dropout pass over
@@ -237,49 +217,88 @@ class MyConv1d(nn.Module):
     # relu'(output) (MutanFusion(..., relu_input=True)): the fused backward then skips its own gate.
     grad_pregated = False
 
-    def _fused_ok(self, x):
+    def _check_rank(self, x):
+        if x.dim() != 3:
+            raise ValueError("[error] putils.Conv1d(%s, %s, %s, %s): input_dim (%s) should equal to 3"
+                             % (self.in_channels, self.out_channels, self.kernel_size, self.stride, x.dim()))
+
+    def _k5_ok(self, x):
         return self.fused and self.af in (None, "relu") and x.dim() == 3 and x.is_cuda and x.dtype == torch.float32 \
-            and self.out_channels >= 32 and x.size(0) * x.size(1) >= 1024
+            and self.out_channels >= 32 and x.shape[0] * x.shape[1] >= 1024
+
+    def relation_projection_ok(self, v):
+        """Can ops.relation_projection (the pairwise-relation step and this projection as ONE autograd node) stand in for
+        ops.relation_apply followed by this layer on v [B,N,D]?  Wherever K5 would serve the layer and the node's kernels
+        take the shape."""
+        return self.af == "relu" and self._k5_ok(v) and ops.relation_projection_supported(v, self.conv.weight.squeeze(-1))
+
+    def _bf16_route(self, x, af, p):
+        """Mixed-precision forms (x bf16, last dim possibly zero-padded past in_channels): bf16 operands, fp32
+        accumulate, fp32 master weights.  Wide layers return the output padded to a multiple of 64 (pad = 0) so the
+        next bf16 GEMM needs no tail; narrow ones (the G attention logits) come back as fp32."""
+        if self.out_channels >= 32 and self.bf16_gemm == "engine" and af in (None, "", "relu"):
+            if p and (p != 0.5 or x.requires_grad):
+                # the in-kernel mask exists at p = 0.5 and has no data gradient (compress_v reads the model input); an x
+                # that needs one (compress_v2 behind the pairwise relation, relation_mode=0) is dropped beforehand
+                return _Route("bf16_engine", af, p, 0.0, None)
+            return _Route("bf16_engine", af, 0.0, p, None)
+        return _Route("bf16_library", None, p, 0.0, af)
+
+    def _route(self, x, predropped=False, pre_activation=False):
+        """Which form serves this call, at which dropout rate -> _Route.  Reads the layer's settings and x.is_cuda / dtype /
+        dim() / shape / requires_grad only: nothing is launched and no seed is drawn.  x is 3-D (_check_rank).
+        predropped: the producer of x has applied this layer's input dropout; pre_activation: the caller wants the
+        convolution's output without the layer's activation (MyATT applies its softmax inside K3)."""
+        af = None if pre_activation else self.af
+        p = 0.0 if predropped else _rate(self)
+        bf16 = x.dtype == torch.bfloat16
+        if bf16 and not pre_activation and (predropped or af in (None, "relu")):
+            return self._bf16_route(x, af, p)
+        if not pre_activation and self._k5_ok(x):
+            # large region-side projection (compress_v / compress_v2): dropout + GEMM + bias + relu in ONE kernel
+            # on the fp32 MFMA tile engine (K5); the dropout mask is a counter hash keyed by a seed drawn from
+            # torch's CPU generator, so torch.manual_seed governs it and no mask tensor exists
+            return _Route("k5", af, 0.0, p, None)
+        if not predropped and ops.attention_logits_supported(x, self.in_channels, self.out_channels):
+            # the G attention logits of MyATT: dropout + 1x1 conv in one HIP kernel (K3a), fp32 out for either storage
+            return _Route("logits", None, 0.0, p, af)
+        if bf16:
+            return self._bf16_route(x, None, p)._replace(post=af)
+        if af == "relu" and x.is_cuda and (predropped or x.dtype == torch.float32):
+            return _Route("library", "relu", p, 0.0, None)      # the relu rides in the library GEMM's epilogue (ops.LinearFn)
+        return _Route("library", None, p, 0.0, af)
+
+    def _run(self, x, route, packed=None):
+        form, act, drop, p, post = route
+        w, b = self.conv.weight.squeeze(-1), self.conv.bias
+        if drop:
+            x = F.dropout(x, p=drop, training=True)
+        if form == "logits":
+            y = ops.attention_logits(x, w, b, p, _seed(p))
+        elif form == "k5":
+            y = ops.linear_act(x, w, b, act, p, _seed(p), pregated=self.grad_pregated)
+        elif form == "bf16_engine":
+            y = ops.linear_bf16(x, w, b, act, p, _seed(p), pregated=self.grad_pregated, packed=packed)
+        elif form == "bf16_library":
+            wide = self.out_channels >= 32
+            n_p = ops.pad_to(self.out_channels) if wide else self.out_channels
+            wp = ops.PackedWeightBf16.apply(w, n_p, x.size(-1))
+            bp = F.pad(b, (0, n_p - self.out_channels)).to(torch.bfloat16)
+            y = ops.linear(x, wp, bp)
+            y = y if wide else y.float()
+        else:
+            y = ops.linear(x, w, b, act=act)
+        return _activation(y, post, self.dim)
+
+    def pre_activation(self, x):
+        self._check_rank(x)
+        return self._run(x, self._route(x, pre_activation=True))
 
     def forward(self, x, predropped=False, packed=None):
         """predropped=True: the producer of x has already applied this layer's input dropout (ops.relation_apply).
         packed (bf16 inputs): this layer's shadows from the model's ops.ShadowPlan (else they are packed here)."""
-        if predropped:
-            if x.dim() != 3:
-                raise ValueError("[error] putils.Conv1d(%s, %s, %s, %s): input_dim (%s) should equal to 3"
-                                 % (self.in_channels, self.out_channels, self.kernel_size, self.stride, x.dim()))
-            if x.dtype == torch.bfloat16:
-                return self._linear_bf16(x, self.af, 0.0, packed)
-            if self._fused_ok(x):
-                return ops.linear_act(x, self.conv.weight.squeeze(-1), self.conv.bias, self.af, 0.0, 0,
-                                      pregated=self.grad_pregated)
-            return self._linear_f32(x)
-        if x.dtype == torch.bfloat16 and self.af in (None, "relu"):
-            if x.dim() != 3:
-                raise ValueError("[error] putils.Conv1d(%s, %s, %s, %s): input_dim (%s) should equal to 3"
-                                 % (self.in_channels, self.out_channels, self.kernel_size, self.stride, x.dim()))
-            return self._linear_bf16(x, self.af, self.p if (self.training and self.p) else 0.0, packed)
-        if self._fused_ok(x):
-            # large region-side projection (compress_v / compress_v2): dropout + GEMM + bias + relu in ONE kernel
-            # on the fp32 MFMA tile engine (K5); the dropout mask is a counter hash keyed by a seed drawn from
-            # torch's CPU generator, so torch.manual_seed governs it and no mask tensor exists
-            p = self.p if (self.training and self.p) else 0.0
-            seed = ops.next_dropout_seed() if p else 0
-            return ops.linear_act(x, self.conv.weight.squeeze(-1), self.conv.bias, self.af, p, seed,
-                                  pregated=self.grad_pregated)
-        if self.af == "relu" and x.dim() == 3 and x.dtype == torch.float32 and x.is_cuda and \
-                not ops.attention_logits_supported(x, self.in_channels, self.out_channels):
-            if self.p:
-                x = F.dropout(x, p=self.p, training=self.training)
-            return self._linear_f32(x)
-        return _activation(self.pre_activation(x), self.af, self.dim)
-
-    def _linear_f32(self, x):
-        """af(conv) with a relu riding in the library GEMM's epilogue (ops.LinearFn); other activations as torch ops."""
-        w, b = self.conv.weight.squeeze(-1), self.conv.bias
-        if self.af == "relu" and x.is_cuda:
-            return ops.linear(x, w, b, act="relu")
-        return _activation(ops.linear(x, w, b), self.af, self.dim)
+        self._check_rank(x)
+        return self._run(x, self._route(x, predropped), packed)
 
 
 class MutanFusion(nn.Module):
@@ -307,17 +326,13 @@ class MutanFusion(nn.Module):
         # (bf16 region tensors carry the feature dim zero-padded to a multiple of 64: see ops.pad_to)
         want = ops.pad_to(self.input_dim1) if inputs1.dtype == torch.bfloat16 else self.input_dim1
         if inputs1.size(-1) != want:
-            raise ValueError(
-                "[error] putils.Linear(%s, %s): last dimension of input(%s) should equal to in_features(%s)"
-                % (self.input_dim1, self.hidden_dim, inputs1.size(-1), self.input_dim1))
+            raise _last_dim_error(self.input_dim1, self.hidden_dim, inputs1.size(-1))
         if h2 is None:
             if inputs2.dim() != 2 or inputs2.size(0) != inputs1.size(0):
                 raise ValueError("MutanFusion: inputs2 must be [B, input_dim2] with the batch of inputs1")
             # question side: R small [B,in2]x[in2,H] GEMMs (Linear's own check raises ValueError on a bad last dim)
             if inputs2.size(-1) != self.input_dim2:
-                raise ValueError(
-                    "[error] putils.Linear(%s, %s): last dimension of input(%s) should equal to in_features(%s)"
-                    % (self.input_dim2, self.hidden_dim, inputs2.size(-1), self.input_dim2))
+                raise _last_dim_error(self.input_dim2, self.hidden_dim, inputs2.size(-1))
             h2 = my_linears(list(self.list_linear2), inputs2)                          # [B,R,H], one batched GEMM
         if inputs1.dim() == 2 and inputs1.is_cuda:
             # vector-vector fusion (fusion_final: B rows, not B*N): a few hundred MFLOP, far too little for the K4 tile
@@ -351,8 +366,7 @@ class MyATT(nn.Module):
 
     def glimpse_dropout(self):
         """Input dropout rate of the per-glimpse MyLinear list in the current mode (0.0 in eval)."""
-        first = self.list_linear_v_fusion[0]
-        return float(first.p) if (self.training and getattr(first, "p", None)) else 0.0
+        return _rate(self.list_linear_v_fusion[0])
 
     def _fused_dropout_ok(self):
         """The G glimpse layers share one dropout rate (else each draws its own mask at its own rate: the batched form and
@@ -367,7 +381,6 @@ class MyATT(nn.Module):
         grouped: the caller runs the grouped head; under VQA_HEAD=grouped the projections are a phase of it
         (head.GlimpseProjections) -- ONLY when the consumer of the result is the head's fusion phase, which hands the
         gradient back gated by the relu (gating it again, as the batched form does, changes nothing)."""
-        from . import head
         if grouped and head.glimpses_grouped():
             mods = list(self.list_linear_v_fusion)
             pd = self.glimpse_dropout()
@@ -396,22 +409,21 @@ class MyATT(nn.Module):
         if pooled_map is None and inputs.is_cuda and (pd > 0 or return_pooled) and self._fused_dropout_ok():
             # the glimpse projections' input dropout rides in the pooling kernel's store (one pass fewer each way), and
             # glimpse 0 comes back undropped as its own tensor for the caller (CoR2's relation step)
-            res = ops.softmax_attention_pool_drop(logits, inputs, pd, ops.next_dropout_seed() if pd else 0, return_pooled, **counts)
+            res = ops.softmax_attention_pool_drop(logits, inputs, pd, _seed(pd), return_pooled, **counts)
             alpha, pooled = res[0], res[1]
-            x_v = self.glimpse_projection(pooled, predropped=True, grouped=grouped)
             if return_pooled:
-                return x_v, torch.split(alpha, 1, dim=2), alpha, res[2]
-            return x_v, torch.split(alpha, 1, dim=2), alpha
-        alpha, pooled = ops.softmax_attention_pool(logits, inputs, **counts)           # [B,N,G], [B,G,D]
-        if return_pooled:       # glimpse 0 for the caller (CoR2's relation step), the whole tensor for the projections
-            pooled, first = ops.with_first_group(pooled)
-        if pooled_map is None:
-            x_v = self.glimpse_projection(pooled, grouped=grouped)
+                first = res[2]
+            x_v = self.glimpse_projection(pooled, predropped=True, grouped=grouped)
         else:
-            x_v = self.glimpse_projection(pooled_map(pooled, self.glimpse_dropout()), predropped=True, grouped=grouped)
-        if return_pooled:
-            return x_v, torch.split(alpha, 1, dim=2), alpha, first
-        return x_v, torch.split(alpha, 1, dim=2), alpha
+            alpha, pooled = ops.softmax_attention_pool(logits, inputs, **counts)           # [B,N,G], [B,G,D]
+            if return_pooled:       # glimpse 0 for the caller (CoR2's relation step), the whole tensor for the projections
+                pooled, first = ops.with_first_group(pooled)
+            if pooled_map is None:
+                x_v = self.glimpse_projection(pooled, grouped=grouped)
+            else:
+                x_v = self.glimpse_projection(pooled_map(pooled, pd), predropped=True, grouped=grouped)
+        out = (x_v, torch.split(alpha, 1, dim=2), alpha)
+        return out + (first,) if return_pooled else out
 
     def forward(self, inputs, fuse, lens=None):
         x_v, list_att, _ = self.attend(inputs, self.conv_att.pre_activation(fuse), lens=lens)
@@ -491,3 +503,73 @@ def question_feature(seq2vec, q):
     if torch.is_floating_point(q) and q.dim() == 2 and q.size(-1) == 2400:
         return q
     return seq2vec(q)
+
+
+class RegionQuestionModel(nn.Module):
+    """What cor2.Model and oda.Model share around their own reasoning steps: the question-encoder slot, the region input,
+    the cut between an early and a late part of backward, and the grouped head's last two phases.  Holds no parameter or
+    buffer of its own."""
+
+    compute_dtype = torch.float32       # storage type of the region-side tensors (cor2.Model sets its own)
+
+    def _set_seq2vec(self, seq2vec, vocab_words, encoder_dtype, encoder_input_dtype):
+        """The ``seq2vec`` slot: "skipthoughts" (the reference's encoder, config/CoR2.py:166, randomly initialised here),
+        "vector" / None (sample['q_idxes'] holds the 2400-d question vector) or the caller's own module."""
+        if seq2vec == "skipthoughts":
+            from .encoder import SkipThoughts, encoder_dtype_from, encoder_input_dtype_from
+            seq2vec = SkipThoughts(vocab_list=vocab_words, gru="BayesianGRU", return_last=True, af="relu",
+                                   compute_dtype=encoder_dtype_from(encoder_dtype),
+                                   input_dtype=encoder_input_dtype_from(encoder_input_dtype))
+        elif encoder_dtype is not None or encoder_input_dtype is not None:
+            given = seq2vec if seq2vec is None or isinstance(seq2vec, str) else type(seq2vec).__name__
+            raise ValueError("%s configures the SkipThoughts encoder that seq2vec='skipthoughts' builds; "
+                             "it cannot be given with seq2vec=%r"
+                             % ("encoder_dtype" if encoder_dtype is not None else "encoder_input_dtype", given))
+        if seq2vec == "vector":
+            seq2vec = None
+        self.seq2vec = seq2vec if seq2vec is not None else QuestionVectorInput(2400)
+
+    def _region_input(self, sample, counts=True):
+        """-> (v [B,N,2048], v_len).  v_len: sample['v_len'] (optional, read when `counts`) -- the number of real regions of
+        every sample, the rest of its N rows being (finite) padding -- as the int32 device tensor the masked kernels read
+        (ops.region_counts), else None.  bf16 regions on their way into an fp32 model are the feed's transport format
+        (feed.store_batches(region_dtype=torch.bfloat16): half the host -> device bytes), widened exactly by one HIP pass."""
+        v = sample["v"]
+        b = v.size(0)
+        v = v.contiguous().view(b, -1, 2048)
+        v_len = sample.get("v_len") if counts else None
+        if v_len is not None:
+            if not isinstance(v_len, torch.Tensor) or v_len.dim() != 1 or v_len.size(0) != b:
+                raise ValueError("v_len must be [B] = [%d], got %s"
+                                 % (b, tuple(v_len.shape) if isinstance(v_len, torch.Tensor) else type(v_len)))
+            v_len = ops.region_counts(v_len, v.size(1), v.device)
+        if v.is_cuda and v.dtype == torch.bfloat16 and self.compute_dtype == torch.float32:
+            v = ops.widen_bf16(v)
+        return v, v_len
+
+    def forward_with_cut(self, sample):
+        """-> (logits, outs, ins): ``outs`` are the results of the early part of the model that the late part
+        (``late_parameters``) reads, ``ins`` the detached aliases it actually consumed.  d loss / d ins fed as grad_outputs
+        of ``outs`` completes the backward."""
+        cut = []
+        logits = self(sample, cut)
+        return logits, cut[0], cut[1]
+
+    @staticmethod
+    def _cut_aliases(cut, outs):
+        """The late part runs on detached aliases of `outs`, so a backward pass from the loss ends at the aliases (some of
+        the originals may be ancestors of others and would otherwise drag the early layers into it); a second pass then
+        carries the aliases' gradients from the originals to the inputs (trainer.DataParallelTrainer, overlap=True)."""
+        ins = [t.detach().requires_grad_(t.requires_grad) for t in outs]
+        cut.extend([outs, ins])
+        return ins
+
+    def _grouped_tail(self, h2_final, *inputs):
+        """The grouped head's last two phases: fusion_final (its first input is cat(inputs), never materialised) with the
+        rank product and the classifier's input dropout in its epilogue, then the classifier -- one seed for both."""
+        p_c = _rate(self.linear_classif)
+        seed = _seed(p_c)
+        lins = list(self.fusion_final.list_linear1)
+        x = head.VectorFusion.apply(h2_final, p_c, seed, len(inputs), *inputs, *[l.linear.weight for l in lins],
+                                    *[l.linear.bias for l in lins])
+        return head.Classifier.apply(x, self.linear_classif.linear.weight, self.linear_classif.linear.bias, p_c, seed)

@@ -7,13 +7,13 @@ its dropout mask are never built: HIP kernel K2 contracts them against the atten
 import os
 
 import torch
-import torch.nn as nn
 
 from . import head, ops
-from .layers import MutanFusion, MyATT, MyConv1d, MyLinear, QuestionVectorInput, linear_stack_groups, my_linears, question_feature
+from .layers import MutanFusion, MyATT, MyConv1d, MyLinear, RegionQuestionModel, _rate, _seed, linear_stack_groups, my_linears, \
+    question_feature
 
 
-class Model(nn.Module):
+class Model(RegionQuestionModel):
     def __init__(self, vocab_words=None, num_ans=None, seq2vec=None, regions=36, encoder_dtype=None, encoder_input_dtype=None,
                  region_counts=False):
         super().__init__()
@@ -25,19 +25,7 @@ class Model(nn.Module):
         # samples with more than j regions only.  False: the key is refused, as before.
         self.region_counts = bool(region_counts)
 
-        if seq2vec == "skipthoughts":      # the reference's encoder (config/CoR2.py:166), randomly initialised here
-            from .encoder import SkipThoughts, encoder_dtype_from, encoder_input_dtype_from
-            seq2vec = SkipThoughts(vocab_list=vocab_words, gru="BayesianGRU", return_last=True, af="relu",
-                                   compute_dtype=encoder_dtype_from(encoder_dtype),
-                                   input_dtype=encoder_input_dtype_from(encoder_input_dtype))
-        elif encoder_dtype is not None or encoder_input_dtype is not None:
-            given = seq2vec if seq2vec is None or isinstance(seq2vec, str) else type(seq2vec).__name__
-            raise ValueError("%s configures the SkipThoughts encoder that seq2vec='skipthoughts' builds; "
-                             "it cannot be given with seq2vec=%r"
-                             % ("encoder_dtype" if encoder_dtype is not None else "encoder_input_dtype", given))
-        if seq2vec == "vector":             # explicit pass-through slot: sample['q_idxes'] holds the 2400-d question vector
-            seq2vec = None
-        self.seq2vec = seq2vec if seq2vec is not None else QuestionVectorInput(2400)
+        self._set_seq2vec(seq2vec, vocab_words, encoder_dtype, encoder_input_dtype)
         self.compress_v = MyConv1d(2048, 310, 1, 1, p=0.5, af="relu")
         self.compress_q = MyLinear(2400, 310, p=0.5, af="relu")
         self.att = MyATT(fuse_dim=regions * 310, glimpses=4, inputs_dim=2048, att_dim=620, af="relu")
@@ -58,13 +46,9 @@ class Model(nn.Module):
         """config/ODA.py:216-222 + the dropout/1x1-conv of conv_att (config/ODA.py:149), fused (K2).
         lens (optional): int32 [B] device tensor of region counts (ops.region_counts): the masked K2."""
         conv = self.att.conv_att
-        p = conv.p if (self.training and conv.p) else 0.0
-        seed = 0
-        if p:
-            # fresh mask every call, drawn from torch's generator so torch.manual_seed governs it
-            seed = ops.next_dropout_seed()
+        p = _rate(conv)
         w = conv.conv.weight.view(conv.out_channels, -1)
-        return ops.object_difference_attention(v_feature_low, q_feature_low, w, conv.conv.bias, p, seed,
+        return ops.object_difference_attention(v_feature_low, q_feature_low, w, conv.conv.bias, p, _seed(p),
                                                gate_dvl=self.compress_v.grad_pregated, lens=lens)
 
     def _grouped_head_ok(self, q_feature, cut):
@@ -80,32 +64,15 @@ class Model(nn.Module):
         before backward enters the attention and the region projection (see cor2.CoR2Model.late_parameters)."""
         return [p for m in (self.fusion_final, self.linear_classif) for p in m.parameters()]
 
-    def forward_with_cut(self, sample):
-        """-> (logits, outs, ins) as cor2.CoR2Model.forward_with_cut: the cut is (attended features, q_final)."""
-        cut = []
-        logits = self(sample, cut)
-        return logits, cut[0], cut[1]
-
     def forward(self, sample, _cut=None):
         if "v_len" in sample and not self.region_counts:
             # the attention weights of this model are indexed by region slot (fuse_dim = regions * 310): masking them changes
             # which samples train which slot, so the model reads the counts only when it was built to
             raise ValueError("ODA.Model takes no per-sample region counts: drop 'v_len' from the sample, or build the model "
                              "with region_counts=True (CoR2Model masks with it)")
-        v = sample["v"]
-        b = v.size(0)
-        v_feature = v.contiguous().view(b, -1, 2048)
-        # 'v_len' (region_counts=True, optional): the number of real regions of every sample, the rest of its N rows being
-        # (finite) padding.  The masked K2 sums differences over the real rows only and writes exact zeros on the padding, the
-        # masked K3 gives the padding alpha = 0; without the key the model runs unmasked.
-        v_len = sample.get("v_len") if self.region_counts else None
-        if v_len is not None:
-            if not isinstance(v_len, torch.Tensor) or v_len.dim() != 1 or v_len.size(0) != b:
-                raise ValueError("v_len must be [B] = [%d], got %s"
-                                 % (b, tuple(v_len.shape) if isinstance(v_len, torch.Tensor) else type(v_len)))
-            v_len = ops.region_counts(v_len, v_feature.size(1), v_feature.device)
-        if v_feature.dtype == torch.bfloat16 and v_feature.is_cuda:      # the feed's bf16 transport format, widened exactly (ops.widen_bf16)
-            v_feature = ops.widen_bf16(v_feature)
+        # 'v_len' (region_counts=True, optional): the masked K2 sums differences over the real rows only and writes exact zeros
+        # on the padding, the masked K3 gives the padding alpha = 0; without the key the model runs unmasked.
+        v_feature, v_len = self._region_input(sample, counts=self.region_counts)
         if v_feature.size(1) != self.regions:
             raise ValueError("ODA.Model was built for %d regions, input has %d" % (self.regions, v_feature.size(1)))
         q_feature = question_feature(self.seq2vec, sample["q_idxes"] if "q_idxes" in sample else sample["q"])
@@ -116,9 +83,9 @@ class Model(nn.Module):
             # the [B,.]-sized layers as grouped phases (head.py): the two question projections (the object-difference kernel
             # reads the first one: its gradient comes back ungated), then fusion_final's question-side rank factors
             proj = [self.compress_q, self.linear_q]
-            p_in = float(proj[0].p) if (self.training and proj[0].p) else 0.0
+            p_in = _rate(proj[0])
             q_feature_low, q_final = head.QuestionProjections.apply(
-                q_feature.contiguous(), p_in, ops.next_dropout_seed() if p_in else 0, (), 0.0, 0, (0,),
+                q_feature.contiguous(), p_in, _seed(p_in), (), 0.0, 0, (0,),
                 *[m.linear.weight for m in proj], *[m.linear.bias for m in proj])
             lin2 = list(self.fusion_final.list_linear2)
             (h2_final,) = head.GatesAndRankFactors.apply(2, (), ((1, self.fusion_final.R),), (1.0, 1.0), q_feature_low, q_final,
@@ -132,17 +99,9 @@ class Model(nn.Module):
 
         self.alpha_dict = {"alphas": alphas[0].detach()}
         if grouped:
-            p_c = float(self.linear_classif.p) if (self.training and self.linear_classif.p) else 0.0
-            seed = ops.next_dropout_seed() if p_c else 0
-            lin1 = list(self.fusion_final.list_linear1)
-            x = head.VectorFusion.apply(h2_final, p_c, seed, 1, v_final, *[l.linear.weight for l in lin1],
-                                        *[l.linear.bias for l in lin1])
-            return head.Classifier.apply(x, self.linear_classif.linear.weight, self.linear_classif.linear.bias, p_c, seed)
+            return self._grouped_tail(h2_final, v_final)
 
         if _cut is not None:
-            outs = [v_final, q_final]
-            ins = [t.detach().requires_grad_(t.requires_grad) for t in outs]
-            _cut.extend([outs, ins])
-            v_final, q_final = ins
+            v_final, q_final = self._cut_aliases(_cut, [v_final, q_final])       # the cut is (attended features, q_final)
         x = self.fusion_final(v_final, q_final)
         return self.linear_classif(x)
