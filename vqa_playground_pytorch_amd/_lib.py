@@ -95,7 +95,11 @@ SIGNATURES = {
     "vqa_gemm_nt_split_batched": (_c_i, [_c_f, _c_l, _c_i, _c_f, _c_f, _c_l, _c_i, _c_f, _c_i, _c_f, _c_l, _c_i, _c_i, _c_i, _c_i,
                                          _c_i, _c_i, _c_st]),
     "vqa_host_gather_rows": (_c_i, [_c_f, _c_l, _c_l, ctypes.c_void_p, _c_i, ctypes.c_void_p, _c_i, _c_i]),
+    "vqa_host_gather_ragged": (_c_i, [_c_f, _c_l, _c_l, ctypes.c_void_p, ctypes.c_void_p, _c_l, ctypes.c_void_p, _c_i, ctypes.c_void_p,
+                                      _c_l, ctypes.c_void_p, ctypes.c_void_p, _c_i, _c_i]),
     "vqa_widen_bf16": (_c_i, [_c_f, _c_f, _c_sz, _c_st]),
+    "vqa_unpack_regions_supported": (_c_i, [_c_i, _c_i, _c_i, _c_i, _c_i]),
+    "vqa_unpack_regions": (_c_i, [_c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_st]),
     "vqa_gemm_tn_split_supported": (_c_i, [_c_i, _c_i, _c_i, _c_i, _c_i]),
     "vqa_gemm_tn_split_workspace_bytes": (_c_sz, [_c_i, _c_i, _c_i]),
     "vqa_gemm_tn_split": (_c_i, [_c_f, _c_i, _c_f, _c_i, _c_f, _c_f, _c_sz, _c_i, _c_i, _c_i, _c_st]),

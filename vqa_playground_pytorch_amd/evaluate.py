@@ -43,19 +43,21 @@ class Evaluator:
 
     @staticmethod
     def _model_keys(sample):
-        keys = ("v", "q_idxes") if "q_idxes" in sample else ("v", "q")
+        v = "v_packed" if "v_packed" in sample else "v"              # packed region batches (feed.store_batches(packed=True))
+        keys = (v, "q_idxes") if "q_idxes" in sample else (v, "q")
         return keys + ("v_len",) if "v_len" in sample else keys      # per-sample region counts (cor2.Model.forward)
 
     def _inputs(self, sample):
         """The tensors one pass reads, on the model's device: the model's inputs, the target 'a', the candidates 'a_mc_idx'.
         'v_len' (region counts) is validated when it comes from the host and becomes the int32 device tensor the kernels read,
-        so the replayed forward keeps it in a static input buffer like the rest."""
+        so the replayed forward keeps it in a static input buffer like the rest.  A packed batch's 'v_packed' stands where 'v' does."""
         keys = list(self._model_keys(sample)) + [k for k in ("a", "a_mc_idx") if k in sample]
         inputs = {k: sample[k].to(self.device, non_blocking=True) for k in keys if k != "v_len"}
         if "v_len" in sample:
             from . import ops
-            v = sample["v"]
-            inputs["v_len"] = ops.region_counts(sample["v_len"], v.numel() // (v.size(0) * 2048), self.device)
+            v = sample["v_packed"] if "v_packed" in sample else sample["v"]     # (packed: N rows for every entry of 'v_len')
+            b = sample["v_len"].size(0) if "v_packed" in sample else v.size(0)
+            inputs["v_len"] = ops.region_counts(sample["v_len"], v.numel() // (max(b, 1) * 2048), self.device)
         return inputs
 
     def _pass(self, inputs):

@@ -56,17 +56,37 @@ def _check_count(count, regions, what):
     return count
 
 
-def collate(items, num_ans, pin=False, answers="dense"):
+def _check_packed_keys(batch):
+    if "v_packed" in batch:
+        if "v" in batch:
+            raise ValueError("a batch carries its regions padded ('v') or packed ('v_packed'), not both")
+        if "v_len" not in batch:
+            raise ValueError("'v_packed' needs 'v_len': the region counts are what delimits the samples' rows")
+
+
+def collate(items, num_ans, pin=False, answers="dense", packed=False, regions=None):
     """List of reference-style items {'v' [36,2048], 'q_idxes' [T], 'q_id', 'a_10_idx' or 'a', optionally 'a_mc_idx', optionally
     'v_len' = the number of real (not padding) rows of 'v'} -> one batch dict of
     contiguous host tensors (optionally pinned), the layout Model.forward and the trainer expect.  answers="sparse": instead of the
     dense 'a' [B,num_ans] the pairs of 'a_10_idx' as they are, in record order -- 'a_idx' int32 [B,K] and 'a_val' float32 [B,K], K the
-    batch's largest pair count, shorter rows padded with -1 / 0 (ops.densify defines the format; the trainer takes the two keys)."""
+    batch's largest pair count, shorter rows padded with -1 / 0 (ops.densify defines the format; the trainer takes the two keys).
+    packed=True: a packed region batch -- 'v_packed' [B*N, D] (the items' real rows back to back in a capacity-sized buffer, the
+    rest left unwritten) and 'v_len' instead of 'v'.  The items carry ragged 'v' [n_i, D] (then `regions` = N is given), or padded
+    'v' [N, D] plus 'v_len' (N from the shape unless given)."""
     sparse = _check_answers(answers)
     B = len(items)
     v0 = torch.as_tensor(items[0]["v"])
     mk = (lambda *s, dtype: torch.empty(*s, dtype=dtype).pin_memory()) if pin else (lambda *s, dtype: torch.empty(*s, dtype=dtype))
-    batch = {"v": mk(B, *v0.shape, dtype=torch.float32),
+    if packed:
+        if regions is None and "v_len" not in items[0]:
+            raise ValueError("collate(packed=True): ragged items need regions= (the capacity N per sample)")
+        N = int(v0.shape[0] if regions is None else regions)
+        lens = [_check_count(int(it["v_len"]) if "v_len" in it else int(torch.as_tensor(it["v"]).shape[0]), N, "item %d" % i)
+                for i, it in enumerate(items)]
+        regions_part = {"v_packed": mk(B * N, v0.shape[1], dtype=torch.float32)}
+    else:
+        regions_part = {"v": mk(B, *v0.shape, dtype=torch.float32)}
+    batch = {**regions_part,
              "q_idxes": mk(B, len(items[0]["q_idxes"]), dtype=torch.long),
              "q_id": torch.tensor([int(it.get("q_id", i)) for i, it in enumerate(items)], dtype=torch.long)}
     has_a = "a" in items[0] or "a_10_idx" in items[0]
@@ -93,13 +113,24 @@ def collate(items, num_ans, pin=False, answers="dense"):
             if mc.numel() > MC_CANDIDATES:
                 raise ValueError("item %d has %d multiple-choice candidates, more than %d" % (i, mc.numel(), MC_CANDIDATES))
             batch["a_mc_idx"][i, :mc.numel()] = mc
-    if "v_len" in items[0]:
+    if packed:
+        batch["v_len"] = mk(B, dtype=torch.int32)
+        off = 0
+        for i, (it, n) in enumerate(zip(items, lens)):
+            v = torch.as_tensor(it["v"], dtype=torch.float32)
+            if v.shape[0] < n or v.shape[1:] != v0.shape[1:]:
+                raise ValueError("item %d: 'v' %s does not hold %d rows of %d" % (i, tuple(v.shape), n, v0.shape[1]))
+            batch["v_packed"][off:off + n].copy_(v[:n])
+            batch["v_len"][i] = n
+            off += n
+    elif "v_len" in items[0]:
         # per-item region counts (adaptive features padded to the store's N): int32 [B], what cor2.Model reads as sample['v_len']
         batch["v_len"] = mk(B, dtype=torch.int32)
         for i, it in enumerate(items):
             batch["v_len"][i] = _check_count(int(it["v_len"]), v0.shape[0], "item %d" % i)
     for i, it in enumerate(items):
-        batch["v"][i].copy_(torch.as_tensor(it["v"], dtype=torch.float32))
+        if not packed:
+            batch["v"][i].copy_(torch.as_tensor(it["v"], dtype=torch.float32))
         batch["q_idxes"][i].copy_(torch.as_tensor(it["q_idxes"], dtype=torch.long))
         if has_a:
             if "a" in it:
@@ -110,11 +141,22 @@ def collate(items, num_ans, pin=False, answers="dense"):
 
 
 def shard(batch, rank, world):
-    """Rank r's contiguous slice [r*B/P, (r+1)*B/P) of every tensor of a global batch (SURVEY 8e partitioning)."""
+    """Rank r's contiguous slice [r*B/P, (r+1)*B/P) of every tensor of a global batch (SURVEY 8e partitioning).  A packed batch
+    ('v_packed' + 'v_len'): the rank's samples start at row off[r*B/P] of the global buffer (off = the exclusive prefix sum of
+    'v_len') and its 'v_packed' is the view of (B/P)*N rows from there -- a capacity again, of which the rank's own sum of counts
+    is meaningful; it cannot run past the global buffer, since off[b] <= b*N.  (DataParallelTrainer.shard is per tensor and
+    cannot do this: packed batches are sharded here.)"""
+    _check_packed_keys(batch)
     if world == 1:
         return batch
     out = {}
     for k, t in batch.items():
+        if k == "v_packed":
+            B = batch["v_len"].size(0)
+            per, N = B // world, t.size(0) // B
+            start = int(batch["v_len"][:rank * per].sum())
+            out[k] = t[start:start + per * N]
+            continue
         per = t.size(0) // world
         out[k] = t[rank * per:(rank + 1) * per]
     return out
@@ -162,7 +204,14 @@ class DevicePrefetcher:
         # The slots are sized by the first batch.  The reference's DataLoader has no drop_last (datasets.py:975), so the
         # last batch of an epoch is shorter: it is staged into / yielded as the leading rows of the slot buffers (a plain
         # copy_ would raise on the size mismatch -- or, for a remainder of ONE sample, silently broadcast it).
-        src, dev = {}, {}
+        # A packed batch's 'v_packed' is a capacity buffer of which the first R = sum(v_len) rows mean something: only those are
+        # staged and copied (R from the host-side 'v_len', in hand here) -- the padding never crosses the bus; the device slot is
+        # allocated at capacity and yielded whole (what lies behind row R there is never read).
+        _check_packed_keys(batch)
+        live = int(batch["v_len"].sum()) if "v_packed" in batch else None
+        if live is not None and live > batch["v_packed"].size(0):
+            raise ValueError("prefetcher: 'v_len' sums to %d rows, 'v_packed' holds %d" % (live, batch["v_packed"].size(0)))
+        src, dev, copies = {}, {}, {}
         for k, t in batch.items():
             full = s["dev"][k]
             if t.shape[1:] != full.shape[1:] or t.dtype != full.dtype or t.size(0) > full.size(0):
@@ -175,18 +224,24 @@ class DevicePrefetcher:
                 if k not in s["host"] or s["host"][k].shape[1:] != t.shape[1:] or s["host"][k].size(0) < b:
                     s["host"][k] = torch.empty_like(t).pin_memory()
                 stage = s["host"][k].narrow(0, 0, b)
-                stage.copy_(t)                          # pageable -> pinned staging slot (a host memcpy: ~10 GB/s)
+                rows = b if k != "v_packed" else live
+                stage.narrow(0, 0, rows).copy_(t.narrow(0, 0, rows))     # pageable -> pinned staging slot (a host memcpy: ~10 GB/s)
                 src[k] = stage
             dev[k] = full.narrow(0, 0, b) if b != full.size(0) else full
+            copies[k] = (dev[k], src[k]) if k != "v_packed" else (dev[k].narrow(0, 0, live), src[k].narrow(0, 0, live))
         with torch.cuda.stream(self.stream):
             for k in batch:
                 if dev[k].shape != src[k].shape:
                     raise RuntimeError("prefetcher: staging shape %s does not match the batch %s"
                                        % (tuple(dev[k].shape), tuple(src[k].shape)))
-                dev[k].copy_(src[k], non_blocking=True)
+                self._copy(k, *copies[k])
             s["ready"].record(self.stream)
         self.queue.append((s, dev))
         return True
+
+    def _copy(self, key, dst, src):
+        """one host -> device copy of a batch entry, on the copy stream (the views say how many bytes cross the bus)"""
+        dst.copy_(src, non_blocking=True)
 
     def __iter__(self):
         for _ in range(self.depth):
@@ -212,41 +267,75 @@ class FeatureStore:
     tensor [B,N,D] fp32, or bf16 -- then the rows are rounded on the way, half the PCIe bytes for the bf16 path) with `workers`
     threads; nothing is read until a row is asked for (the file stays on disk / in the page cache, like the reference's
     h5py handle with load_mem=None, datasets.py:565-566).  counts: the images' region counts (1..N each, ValueError otherwise) for a
-    store of zero-padded adaptive features; store_batches then serves them as 'v_len'."""
+    store of zero-padded adaptive features; store_batches then serves them as 'v_len'.
 
-    def __init__(self, path, names=None, shape=None, offset=0, workers=4, counts=None):
+    offsets: the RAGGED store, the form adaptive features usually come in -- `path` then holds [total_rows, D] float32, the images'
+    rows back to back with no padding, and offsets (a `.npy` path or an array) n_img + 1 non-decreasing int64 values with
+    offsets[-1] == total_rows: image i owns rows offsets[i] .. offsets[i+1].  regions= gives N, the most rows an image may have
+    (every count must lie in 1..N); counts are the differences of offsets, sample_shape stays (N, D) and len() is the image count.
+    Such a store serves packed batches (gather_packed, store_batches(packed=True)); so does a padded store with counts=, whose
+    gather then takes the first `count` rows of every image."""
+
+    def __init__(self, path, names=None, shape=None, offset=0, workers=4, counts=None, offsets=None, regions=None):
         if shape is None:
             self.features = np.load(path, mmap_mode="r")
         else:
             self.features = np.memmap(path, dtype=np.float32, mode="r", offset=int(offset), shape=tuple(int(x) for x in shape))
-        if self.features.ndim != 3 or self.features.dtype != np.float32:
+        self.ragged = offsets is not None
+        if self.ragged:
+            counts = self._open_ragged(path, offsets, regions, counts)
+        elif self.features.ndim != 3 or self.features.dtype != np.float32:
             raise ValueError("feature store %s: expected a float32 [n_img, regions, dim] array, got %s %s"
                              % (path, self.features.dtype, self.features.shape))
+        else:
+            self._n_img, self._sample_shape = self.features.shape[0], tuple(self.features.shape[1:])
+            self._starts = None        # (a padded store's row starts, i * N: built when it first serves a packed batch)
         if isinstance(names, (str, os.PathLike)):
             with open(names, encoding="utf-8") as fh:                          # utils.file2data(..., 'txt'): utils.py:452-454
                 names = fh.read().split("\n")[:-1]
         self.idx_to_name = list(names) if names is not None else None
         self.name_to_idx = {n: i for i, n in enumerate(self.idx_to_name)} if names is not None else None
-        if self.idx_to_name is not None and len(self.idx_to_name) != self.features.shape[0]:
-            raise ValueError("feature store %s: %d names for %d feature rows" % (path, len(self.idx_to_name), self.features.shape[0]))
+        if self.idx_to_name is not None and len(self.idx_to_name) != self._n_img:
+            raise ValueError("feature store %s: %d names for %d feature rows" % (path, len(self.idx_to_name), self._n_img))
         # counts (optional): a `.npy` path or an array of [n_img] integers, the number of real regions of every image (adaptive
         # bottom-up features: 10..100 boxes).  The rows beyond an image's count are handed out as the file holds them, so the
         # store must be ZERO-PADDED there (the models only ask for finite values; zeros are the contract).
         self.counts = None
         if counts is not None:
             c = np.load(counts) if isinstance(counts, (str, os.PathLike)) else np.asarray(counts)
-            if c.ndim != 1 or c.shape[0] != self.features.shape[0] or not np.issubdtype(c.dtype, np.integer):
-                raise ValueError("feature store %s: counts must be %d integers, got %s %s" % (path, self.features.shape[0], c.dtype, c.shape))
-            if c.size and (c.min() < 1 or c.max() > self.features.shape[1]):
+            if c.ndim != 1 or c.shape[0] != self._n_img or not np.issubdtype(c.dtype, np.integer):
+                raise ValueError("feature store %s: counts must be %d integers, got %s %s" % (path, self._n_img, c.dtype, c.shape))
+            if c.size and (c.min() < 1 or c.max() > self._sample_shape[0]):
                 raise ValueError("feature store %s: region counts %d..%d outside 1..%d"
-                                 % (path, int(c.min()), int(c.max()), self.features.shape[1]))
-            self.counts = c.astype(np.int32)
+                                 % (path, int(c.min()), int(c.max()), self._sample_shape[0]))
+            self.counts = np.ascontiguousarray(c.astype(np.int32))
         self.workers = max(1, int(workers))
         self._pool = ThreadPoolExecutor(self.workers) if self.workers > 1 else None
         self._lock = threading.Lock()
 
+    def _open_ragged(self, path, offsets, regions, counts):
+        """checks of the ragged form -> the counts (the differences of offsets)"""
+        if counts is not None:
+            raise ValueError("feature store %s: offsets= already says the counts; do not pass counts= as well" % path)
+        if regions is None or int(regions) < 1:
+            raise ValueError("feature store %s: a ragged store needs regions= (N, the most rows an image may have)" % path)
+        if self.features.ndim != 2 or self.features.dtype != np.float32:
+            raise ValueError("feature store %s: with offsets= expected a float32 [total_rows, dim] array, got %s %s"
+                             % (path, self.features.dtype, self.features.shape))
+        o = np.load(offsets) if isinstance(offsets, (str, os.PathLike)) else np.asarray(offsets)
+        if o.ndim != 1 or o.size < 2 or not np.issubdtype(o.dtype, np.integer):
+            raise ValueError("feature store %s: offsets must be n_img + 1 integers, got %s %s" % (path, o.dtype, o.shape))
+        o = np.ascontiguousarray(o.astype(np.int64))
+        if o[0] != 0 or o[-1] != self.features.shape[0]:
+            raise ValueError("feature store %s: offsets run %d..%d, the array holds %d rows" % (path, int(o[0]), int(o[-1]), self.features.shape[0]))
+        if (np.diff(o) < 0).any():
+            raise ValueError("feature store %s: offsets must not decrease" % path)
+        self._n_img, self._sample_shape = o.size - 1, (int(regions), int(self.features.shape[1]))
+        self._starts = np.ascontiguousarray(o[:-1])
+        return np.diff(o)                  # (1..N each: checked with the counts of a padded store)
+
     def __len__(self):
-        return self.features.shape[0]
+        return self._n_img
 
     def populate(self):
         """Map every page of the store into this process now (MADV_POPULATE_READ where the kernel has it, else one read per 4 KiB
@@ -268,7 +357,7 @@ class FeatureStore:
 
     @property
     def sample_shape(self):
-        return tuple(self.features.shape[1:])
+        return self._sample_shape
 
     def index(self, img_filename):
         """datasets.py:912: `outer.data['img']['name_to_idx'][item_vqa['img_filename']]` (KeyError for an unknown image)."""
@@ -276,6 +365,8 @@ class FeatureStore:
 
     def gather(self, indices, out):
         """out[r] = feature[indices[r]] (rows of N x D floats), fp32 or rounded to bf16 (nearest even), on `workers` threads."""
+        if self.ragged:
+            raise ValueError("gather: a ragged store (offsets=) holds no padded rows; it serves packed batches (gather_packed)")
         idx = np.asarray(indices, dtype=np.int64)
         if idx.ndim != 1 or out.shape[0] < idx.size or tuple(out.shape[1:]) != self.sample_shape:
             raise ValueError("gather: out %s does not take %d rows of %s" % (tuple(out.shape), idx.size, self.sample_shape))
@@ -314,6 +405,61 @@ class FeatureStore:
         if out.dtype == torch.bfloat16:
             out[:n].copy_(torch.from_numpy(dst[:n]))
         return out[:n]
+
+
+    def gather_packed(self, indices, out, v_len_out, native=True):
+        """The packed form of gather: the real rows of images `indices`, back to back, into out [capacity, D] (a pinned host tensor,
+        fp32, or bf16 -- rounded to nearest even on the way), their counts into v_len_out (int32, at least len(indices) long).
+        -> R, the number of rows written; rows of `out` from R on are left as they are.  A ragged store copies offsets[i] ..
+        offsets[i+1], a padded store with counts= the first counts[i] rows of image i.  ONE native call for the batch
+        (csrc/feed_host.hip, vqa_host_gather_ragged: the destination prefix sum once, the copy split over `workers` threads by
+        bytes); native=False, or no library: the same in numpy.  Everything is range-checked before a byte is copied: the indices
+        (IndexError), R against the capacity (ValueError)."""
+        if self.counts is None:
+            raise ValueError("gather_packed: the store has no region counts (FeatureStore(counts=) or (offsets=, regions=))")
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64))
+        N, D = self.sample_shape
+        if idx.ndim != 1 or out.dim() != 2 or out.shape[1] != D or not out.is_contiguous():
+            raise ValueError("gather_packed: out %s is not a contiguous [capacity, %d] buffer" % (tuple(out.shape), D))
+        if out.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("gather_packed: out must be float32 or bfloat16")
+        if v_len_out.dtype != torch.int32 or v_len_out.dim() != 1 or v_len_out.numel() < idx.size or not v_len_out.is_contiguous():
+            raise ValueError("gather_packed: v_len_out must be a contiguous int32 tensor of at least %d entries" % idx.size)
+        if idx.size and (idx.min() < 0 or idx.max() >= len(self)):
+            raise IndexError("gather_packed: feature index out of range [0, %d)" % len(self))
+        lens = self.counts[idx]
+        R = int(lens.sum(dtype=np.int64))
+        if R > out.shape[0]:
+            raise ValueError("gather_packed: the batch has %d rows, out holds %d" % (R, out.shape[0]))
+        if self._starts is None:
+            with self._lock:
+                if self._starts is None:
+                    self._starts = np.arange(len(self), dtype=np.int64) * N
+        if idx.size == 0:
+            return 0
+        rows = self.features.reshape(-1, D)          # (a view: the padded store's [n_img * N, D])
+        L_ = None
+        if native and rows.flags["C_CONTIGUOUS"]:
+            from . import _lib
+            try:
+                L_ = _lib.lib()
+            except _lib.VqaLibraryError:
+                L_ = None
+        if L_ is not None:
+            import ctypes
+            total = ctypes.c_long(0)
+            _lib.check(L_.vqa_host_gather_ragged(rows.ctypes.data, rows.shape[0], D, self._starts.ctypes.data, self.counts.ctypes.data,
+                                                 len(self), idx.ctypes.data, idx.size, out.data_ptr(), out.shape[0],
+                                                 v_len_out.data_ptr(), ctypes.addressof(total), int(out.dtype == torch.bfloat16),
+                                                 self.workers), "host_gather_ragged")
+            return int(total.value)
+        v_len_out.numpy()[:idx.size] = lens
+        src = np.concatenate([np.arange(s, s + n) for s, n in zip(self._starts[idx], lens)])
+        if out.dtype == torch.float32:
+            np.take(rows, src, axis=0, out=out.numpy()[:R], mode="clip")       # (range-checked above)
+        else:
+            out[:R].copy_(torch.from_numpy(rows[src]))
+        return R
 
 
 class _QaTable:
@@ -392,7 +538,7 @@ def qa_table(store, qa_items, num_ans, q_dtype=torch.long, require_answers=False
 
 
 def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, pin=True, region_dtype=torch.float32, ring=3,
-                  q_dtype=torch.long, prefetch=0, epochs=1, producers=1, answers="dense"):
+                  q_dtype=torch.long, prefetch=0, epochs=1, producers=1, answers="dense", packed=False):
     """The reference's loader (datasets.py:893-977: `Inner.__getitem__` + DataLoader(batch_size, shuffle, pin_memory=True), no
     drop_last) over a FeatureStore: yields batch dicts {'v' [B,N,D], 'q_idxes' [B,T], 'q_id' [B], 'a' [B,num_ans]} of host tensors.
     qa_items: the reference's per-question records -- 'img_filename' (or 'v_idx'), 'q_idxes', 'q_id', 'a_10_idx' [(answer id,
@@ -410,8 +556,16 @@ def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, p
     as they are, 'a_idx' int32 [B,K] and 'a_val' float32 [B,K] in the same staging ring (K = the table's largest pair count, at most
     16; shorter rows padded with -1 / 0, pairs in record order): no dense [B,num_ans] row is allocated, filled or copied, the
     trainer computes its loss from the pairs (ops.densify defines the format).  Records given with a dense 'a' cannot be served sparse.
-    A store with region counts (FeatureStore(counts=...)) adds 'v_len' int32 [B] to every batch, from the same staging ring."""
+    A store with region counts (FeatureStore(counts=...)) adds 'v_len' int32 [B] to every batch, from the same staging ring.
+    packed=True (a store with counts, padded or ragged): instead of 'v' the batches carry 'v_packed', the ring slot's capacity
+    tensor [batch_size*N, D] of which the first sum(v_len) rows are the samples' real rows back to back (the rest is whatever the
+    slot held: nothing reads it) -- the padding is neither gathered nor, through DevicePrefetcher, copied to the device; the
+    models unpack it there (ops.unpack_regions).  The short last batch yields the leading B_last*N rows."""
     sparse = _check_answers(answers)
+    if packed and store.counts is None:
+        raise ValueError("store_batches(packed=True) needs a store with region counts (FeatureStore(counts=) or (offsets=, regions=))")
+    if not packed and getattr(store, "ragged", False):
+        raise ValueError("store_batches: a ragged store (offsets=) serves packed batches only: pass packed=True")
     n = len(qa_items.rows) if isinstance(qa_items, _QaTable) else len(qa_items)
 
     def order_of(epoch):
@@ -434,15 +588,21 @@ def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, p
         b = len(ids)
         with slot_lock:
             while len(slots) <= k:
-                slots.append({"v": mk(batch_size, *store.sample_shape, dtype=region_dtype), "q_idxes": mk(batch_size, T, dtype=q_dtype),
+                v_shape = (batch_size * store.sample_shape[0], store.sample_shape[1]) if packed else (batch_size, *store.sample_shape)
+                slots.append({"v": mk(*v_shape, dtype=region_dtype), "q_idxes": mk(batch_size, T, dtype=q_dtype),
                               "a": mk(batch_size, num_ans, dtype=torch.float32) if has_a and not sparse else None,
                               "a_idx": mk(batch_size, K, dtype=torch.int32) if K else None,
                               "a_val": mk(batch_size, K, dtype=torch.float32) if K else None,
                               "v_len": mk(batch_size, dtype=torch.int32) if store.counts is not None else None})
         s = slots[k]
-        batch = {"v": store.gather(table.rows[ids], s["v"]), "q_idxes": s["q_idxes"][:b], "q_id": torch.from_numpy(table.q_ids[ids])}
+        if packed:
+            store.gather_packed(table.rows[ids], s["v"], s["v_len"])
+            batch = {"v_packed": s["v"][:b * store.sample_shape[0]], "v_len": s["v_len"][:b]}
+        else:
+            batch = {"v": store.gather(table.rows[ids], s["v"])}
+        batch.update({"q_idxes": s["q_idxes"][:b], "q_id": torch.from_numpy(table.q_ids[ids])})
         batch["q_idxes"].numpy()[...] = table.q[ids]
-        if store.counts is not None:
+        if store.counts is not None and not packed:
             batch["v_len"] = s["v_len"][:b]
             batch["v_len"].numpy()[...] = store.counts[table.rows[ids]]
         if K:

@@ -533,7 +533,13 @@ class RegionQuestionModel(nn.Module):
         """-> (v [B,N,2048], v_len).  v_len: sample['v_len'] (optional, read when `counts`) -- the number of real regions of
         every sample, the rest of its N rows being (finite) padding -- as the int32 device tensor the masked kernels read
         (ops.region_counts), else None.  bf16 regions on their way into an fp32 model are the feed's transport format
-        (feed.store_batches(region_dtype=torch.bfloat16): half the host -> device bytes), widened exactly by one HIP pass."""
+        (feed.store_batches(region_dtype=torch.bfloat16): half the host -> device bytes), widened exactly by one HIP pass.
+        A packed batch carries 'v_packed' [B*N, 2048] (fp32 or bf16: the capacity-sized buffer whose first sum(v_len) rows are the
+        samples' real rows back to back) and the then mandatory 'v_len' instead of 'v': ops.unpack_regions rebuilds the padded
+        tensor, exact zeros on the padding, in one pass -- bf16 rows into an fp32 model widened by that same pass, fp32 rows into
+        a bf16 model unpacked as fp32 and cast where a padded fp32 'v' is."""
+        if "v_packed" in sample:
+            return self._packed_region_input(sample, counts)
         v = sample["v"]
         b = v.size(0)
         v = v.contiguous().view(b, -1, 2048)
@@ -546,6 +552,24 @@ class RegionQuestionModel(nn.Module):
         if v.is_cuda and v.dtype == torch.bfloat16 and self.compute_dtype == torch.float32:
             v = ops.widen_bf16(v)
         return v, v_len
+
+    def _packed_region_input(self, sample, counts):
+        if "v" in sample:
+            raise ValueError("a batch carries its regions padded ('v') or packed ('v_packed'), not both")
+        if not counts:
+            raise ValueError("this model reads no per-sample region counts and so takes no packed batch ('v_packed')")
+        vp, v_len = sample["v_packed"], sample.get("v_len")
+        if v_len is None:
+            raise ValueError("'v_packed' needs 'v_len': the region counts are what delimits the samples' rows")
+        if not isinstance(v_len, torch.Tensor) or v_len.dim() != 1 or v_len.size(0) < 1:
+            raise ValueError("v_len must be [B], got %s" % (tuple(v_len.shape) if isinstance(v_len, torch.Tensor) else type(v_len),))
+        b = v_len.size(0)
+        if not isinstance(vp, torch.Tensor) or vp.dim() != 2 or vp.size(1) != 2048 or vp.size(0) < b or vp.size(0) % b:
+            raise ValueError("v_packed must be [B*N, 2048] with B = %d, got %s"
+                             % (b, tuple(vp.shape) if isinstance(vp, torch.Tensor) else type(vp)))
+        v_len = ops.region_counts(v_len, vp.size(0) // b, vp.device)
+        widen = vp.dtype == torch.bfloat16 and self.compute_dtype == torch.float32
+        return ops.unpack_regions(vp, v_len, b, torch.float32 if widen else vp.dtype), v_len
 
     def forward_with_cut(self, sample):
         """-> (logits, outs, ins): ``outs`` are the results of the early part of the model that the late part

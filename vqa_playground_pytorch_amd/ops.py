@@ -558,6 +558,43 @@ def widen_bf16(x):
     return out
 
 
+def unpack_regions(v_packed, v_len, batch, out_dtype=None):
+    """A packed region batch -> the padded [batch, N, D] tensor the region kernels read (csrc/region_unpack.hip, one launch).
+    v_packed [batch*N, D] fp32 or bf16: the capacity-sized buffer whose first sum(v_len) rows are the samples' real rows back to
+    back; v_len: int32 [batch] on v_packed's device (region_counts).  out[b, i] = v_packed[off[b] + i] for i < v_len[b] with off
+    the exclusive prefix sum of v_len (computed on the device), exact +0.0 on the padding.  out_dtype: v_packed's (default), or
+    float32 for bf16 rows -- widened exactly, the bits of widen_bf16.  No autograd: region features are inputs.  CPU tensors run the
+    same definition in torch (the semantics, for tests and hosts without a GPU)."""
+    out_dtype = v_packed.dtype if out_dtype is None else out_dtype
+    if not isinstance(v_packed, torch.Tensor) or v_packed.dim() != 2 or v_packed.dtype not in _REGION_DTYPES:
+        raise ValueError("v_packed must be a float32 or bfloat16 tensor [B*N, D]")
+    if (v_packed.dtype, out_dtype) not in ((torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16),
+                                           (torch.bfloat16, torch.float32)):
+        raise ValueError("unpack_regions: %s rows into %s (float32 rows are cast by the model, not here)" % (v_packed.dtype, out_dtype))
+    B, D = int(batch), v_packed.size(1)
+    if B < 1 or v_packed.size(0) < B or v_packed.size(0) % B:
+        raise ValueError("v_packed holds %d rows: not a capacity of N rows for each of %d samples" % (v_packed.size(0), B))
+    N = v_packed.size(0) // B
+    if not isinstance(v_len, torch.Tensor) or v_len.shape != (B,) or v_len.dtype != torch.int32 or v_len.device != v_packed.device:
+        raise ValueError("unpack_regions: v_len must be int32 [B] = [%d] on %s (see region_counts)" % (B, v_packed.device))
+    if not v_packed.is_cuda:
+        n = v_len.clamp(0, N).long()
+        off = torch.cumsum(n, 0) - n
+        i = torch.arange(N)
+        real = i[None, :] < n[:, None]
+        rows = torch.where(real, off[:, None] + i[None, :], torch.zeros((), dtype=torch.long))
+        out = v_packed.contiguous()[rows.reshape(-1)].to(out_dtype).view(B, N, D)
+        return torch.where(real[:, :, None], out, torch.zeros((), dtype=out_dtype))
+    v_packed, v_len = v_packed.contiguous(), v_len.contiguous()
+    if v_len.data_ptr() % 16:
+        v_len = v_len.clone()           # (a slice of a larger batch's counts: the kernel wants its three pointers 16-byte aligned)
+    out = torch.empty(B, N, D, device=v_packed.device, dtype=out_dtype)
+    _launch("unpack_regions", (B, N, D, v_packed.dtype == torch.bfloat16, out_dtype == torch.bfloat16),
+            _lib.lib().vqa_unpack_regions, _p(v_packed), _p(v_len), _p(out), B, N, D, int(v_packed.dtype == torch.bfloat16),
+            int(out_dtype == torch.bfloat16))
+    return out
+
+
 def pack_bf16(src, dst, batch_stride, row_stride, col_stride, zero_fill=True, offset=0):
     """fp32 [batch, rows, cols] (or [rows, cols]) -> bf16 scattered into ``dst`` (from element ``offset`` on) with the
     given element strides; with zero_fill that part of ``dst`` is zeroed first (the pads of the padded / transposed

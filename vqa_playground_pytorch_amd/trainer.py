@@ -441,11 +441,13 @@ class DataParallelTrainer:
     def _model_keys(sample):
         """The entries of a sample dict the models read (config/CoR2.py:203-205): feeder batches also carry the target
         'a' and 'q_id', which must not be cloned / re-copied into the graph's input buffers every step."""
-        keys = {"v", "q_idxes"} if "q_idxes" in sample else {"v", "q"}
+        v = "v_packed" if "v_packed" in sample else "v"              # packed region batches (feed.store_batches(packed=True))
+        keys = {v, "q_idxes"} if "q_idxes" in sample else {v, "q"}
         return keys | {"v_len"} if "v_len" in sample else keys       # per-sample region counts (cor2.Model.forward)
 
     def shard(self, tensor):
-        """This rank's contiguous slice of a global-batch tensor (rank r gets [r*B/P, (r+1)*B/P))."""
+        """This rank's contiguous slice of a global-batch tensor (rank r gets [r*B/P, (r+1)*B/P)).  Per tensor, so not for the
+        'v_packed' of a packed batch, whose samples are not equally long: feed.shard(batch, rank, world) shards those."""
         if self.world == 1:
             return tensor
         rank = dist.get_rank(self.group)
@@ -462,12 +464,14 @@ class DataParallelTrainer:
         which KLD and BCE are computed directly and CE draws its label per row and step (``last_labels``)."""
         if isinstance(target, dict):
             target = SparseTarget(target["a_idx"], target["a_val"])
-        if self.hip and sample.get("v_len") is not None and sample["v"].is_cuda:
+        v = sample.get("v_packed", sample.get("v"))
+        if self.hip and sample.get("v_len") is not None and v is not None and v.is_cuda:
             # per-sample region counts: validated (a host tensor) and brought to the int32 device form once, so that the graph
-            # path can keep them in a static input buffer like 'v' and 'q_idxes'
+            # path can keep them in a static input buffer like 'v' and 'q_idxes'.  N of a packed batch is its capacity's:
+            # 'v_packed' holds N rows for every entry of 'v_len'
             from . import ops
-            v = sample["v"]
-            sample = dict(sample, v_len=ops.region_counts(sample["v_len"], v.numel() // (v.size(0) * 2048), v.device))
+            b = sample["v_len"].size(0) if "v_packed" in sample else v.size(0)
+            sample = dict(sample, v_len=ops.region_counts(sample["v_len"], v.numel() // (max(b, 1) * 2048), v.device))
         if self.hip and self.want_graph:
             return self._graph_step(sample, target)
         return self.step_eager(sample, target)
@@ -734,7 +738,8 @@ class DataParallelTrainer:
                 k not in sample or sample[k].shape != t.shape or sample[k].dtype != t.dtype for k, t in g["sample"].items()) or \
                 ("v_len" in sample) != ("v_len" in g["sample"]):
             # a batch of another shape (the last one of an epoch), a batch with region counts after a capture without them (the
-            # graph holds the unmasked kernels) or the other way round, or the model switched between train() and eval() since
+            # graph holds the unmasked kernels) or the other way round, a packed batch ('v_packed') after a capture on padded ones
+            # or the other way round (one of the captured keys is missing), or the model switched between train() and eval() since
             # the capture (dropout is baked into the graph): this step is launched kernel by kernel; the captured graphs
             # stay valid for the regular steps that follow
             return self.step_eager(sample, target)
