@@ -1,8 +1,10 @@
 """What the kernel-level GPU tests (tests/test_gpu_*_kernels.py and their siblings) share, said once: sentinel-filled output
 windows and NaN-padded input windows, the launch-log reader and the C-ABI call wrapper, the exact-integer comparison, the "four
-times the float32 error plus one ulp" bars and the parser of a source file's VQA_LAUNCH( sites.  A plain module that the test
-modules import from by name (`from kernel_harness import _bits, _win, ...`); tests/test_kernel_harness.py shows on the CPU that
-each guard here fails when it should.
+times the float32 error plus one ulp" bars, the parser of a source file's VQA_LAUNCH( sites and the two patches of ops._launch (a
+recording spy, a guard that forbids launches).  The C-ABI call wrapper checks its arguments against the signature bound from the
+header; the header's constants come from _lib.DEFINES.  A plain module that the test modules import from by name (`from
+kernel_harness import _bits, _win, ...`) and that needs no GPU to import; tests/test_kernel_harness.py shows on the CPU that each
+guard here fails when it should.
 
 pytest rewrites assertions in test modules only, so every assert in this file carries its own message."""
 import ctypes
@@ -11,9 +13,11 @@ import re
 import pytest
 import torch
 
+from vqa_playground_pytorch_amd._lib import DEFINES, PARAMS
+
 SENT = -12345.0         # fills every output buffer; what is still SENT afterwards was not written
 PAD = 8                 # elements of sentinel (outputs) or NaN (inputs) in front of and behind every window: 32 bytes fp32, 16 bytes bf16
-E_BADARG, E_UNSUPPORTED = -1, -2
+E_BADARG, E_UNSUPPORTED = DEFINES["VQA_E_BADARG"], DEFINES["VQA_E_UNSUPPORTED"]
 EPS32 = float(torch.finfo(torch.float32).eps)
 EPS_BF16 = 2.0 ** -8
 F32, F64, BF = torch.float32, torch.float64, torch.bfloat16
@@ -102,20 +106,67 @@ def _in(t, ld=None):
 # ---- the launch log ----------------------------------------------------------------------------------------------------------
 def _logged(L, call):
     """run `call` -> [(kernel expression without blanks, grid in work-items)] of the launches it made"""
+    cap = DEFINES["VQA_LAUNCH_LOG_CAP"]
     L.vqa_launch_log_reset()
     call()
-    buf = (ctypes.c_ulonglong * 16)()
-    n = L.vqa_launch_log(buf, 16)
-    return [((L.vqa_launch_log_kernel(i) or b"").decode().replace(" ", ""), int(buf[i])) for i in range(min(n, 16))]
+    buf = (ctypes.c_ulonglong * cap)()
+    n = L.vqa_launch_log(buf, cap)
+    return [((L.vqa_launch_log_kernel(i) or b"").decode().replace(" ", ""), int(buf[i])) for i in range(min(n, cap))]
+
+
+_POINTERS = (ctypes.c_void_p, ctypes.c_char_p)
+_FLOATS = (ctypes.c_float, ctypes.c_double)
+_BYREF = type(ctypes.byref(ctypes.c_int()))
+
+
+def check_args(fn, args):
+    """`args` (all of them, the stream included) against fn.argtypes, before the library is entered.  ctypes itself takes extra
+    arguments of a cdecl function in silence and a bare int as a c_void_p -- a size that slipped into a pointer slot would be launched
+    as an address.  Here the count is exact; a pointer slot takes None, a c_void_p, a ctypes array, a pointer or a byref; an integer
+    slot a Python int; a float slot an int or a float; a bool is no number."""
+    name, slots = fn.__name__, fn.argtypes
+    params = PARAMS.get(name, ())
+    assert len(args) == len(slots), "%s takes %d arguments (%s), got %d" % (name, len(slots), ", ".join(params), len(args))
+    for i, (slot, a) in enumerate(zip(slots, args)):
+        number = isinstance(a, (int, float)) and not isinstance(a, bool)
+        if slot in _POINTERS:
+            takes, ok = "a pointer", a is None or isinstance(a, (ctypes.c_void_p, ctypes.Array, ctypes._Pointer, _BYREF))
+        elif slot in _FLOATS:
+            takes, ok = "a number", number
+        else:
+            takes, ok = "an integer", number and isinstance(a, int)
+        got = "%s %r" % (type(a).__name__, a) if number or isinstance(a, bool) else type(a).__name__
+        assert ok, "argument %d (`%s`) of %s takes %s, got %s" % (i + 1, params[i] if i < len(params) else "?", name, takes, got)
 
 
 def _call(ops, fn, *args):
-    """one C-ABI call on torch's current stream -> (return code, launch log), synchronised"""
+    """one C-ABI call on torch's current stream -> (return code, launch log), synchronised; the arguments are checked against
+    the bound signature first (check_args)"""
     L = ops._lib.lib()
+    args += (ops._stream(),)
+    check_args(fn, args)
     rc = []
-    log = _logged(L, lambda: rc.append(fn(*args, ops._stream())))
+    log = _logged(L, lambda: rc.append(fn(*args)))
     torch.cuda.synchronize()
     return rc[0], log
+
+
+# ---- ops._launch, watched or forbidden ---------------------------------------------------------------------------------------
+def spy_launches(monkeypatch, ops):
+    """-> the list that receives (name, shape) of every ops._launch from now on, each forwarded unchanged.  It ends with the
+    test, or with the `monkeypatch.context()` it was given"""
+    seen, inner = [], ops._launch
+
+    def spy(name, shape, *args, **kwargs):
+        seen.append((name, shape))
+        return inner(name, shape, *args, **kwargs)
+
+    monkeypatch.setattr(ops, "_launch", spy)
+    return seen
+
+
+def forbid_launches(monkeypatch, ops):
+    monkeypatch.setattr(ops, "_launch", lambda *a, **k: pytest.fail("a kernel was launched"))
 
 
 def _names(log):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_harness import spy_launches
 from oracle import seeded
 from vqa_playground_pytorch_amd.encoder import BayesianGRU, SkipThoughts
 
@@ -180,15 +181,14 @@ def test_gpu_gru_products_run_on_the_split_engine_at_training_size(rb, lib_optio
     lengths = torch.randint(1, T + 1, (B,), generator=gen)
     gy = torch.randn(B, H, generator=gen)
     xc, xg = x.double().requires_grad_(), x.clone().to(dev).requires_grad_()
-    seen = []
-    inner, bmm = ops._launch, torch.bmm
-    monkeypatch.setattr(ops, "_launch", lambda name, *a, **k: (seen.append(name), inner(name, *a, **k))[1])
-    monkeypatch.setattr(torch, "bmm", lambda *a, **k: (seen.append("torch.bmm"), bmm(*a, **k))[1])
-    yg = gpu(xg, lengths.to(dev))
-    yg.backward(gy.to(dev))
-    monkeypatch.setattr(ops, "_launch", inner)
-    monkeypatch.setattr(torch, "bmm", bmm)
-    assert "torch.bmm" not in seen, "the encoder issued a library GEMM"
+    bmms, bmm = [], torch.bmm
+    with monkeypatch.context() as m:
+        launches = spy_launches(m, ops)
+        m.setattr(torch, "bmm", lambda *a, **k: (bmms.append(1), bmm(*a, **k))[1])
+        yg = gpu(xg, lengths.to(dev))
+        yg.backward(gy.to(dev))
+    seen = [name for name, _ in launches]
+    assert not bmms, "the encoder issued a library GEMM"
     assert seen.count("gemm_nt_split_batched") == 2 * (T - 1) + 2, seen      # T - 1 steps each way (hm_0 = 0), input projections fwd + dx
     assert seen.count("split_weights_pack") == 4 and seen.count("gemm_tn_split") == 6, seen     # 3 recurrent + 3 input weight gradients
     yc = cpu(xc, lengths)

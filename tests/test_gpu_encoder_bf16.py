@@ -18,7 +18,7 @@ import pytest
 import torch
 
 from kernel_harness import (BF, EPS_BF16, E_BADARG, E_UNSUPPORTED, SENT, WorstBar as Bars, _ptr, _same_bits, _sentinel, _untouched, dev,
-                            ops)  # noqa: F401  (ops: the fixture)
+                            ops, spy_launches)  # noqa: F401  (ops: the fixture)
 
 gpu = pytest.mark.gpu
 RTOL_F32 = 2e-4
@@ -351,13 +351,12 @@ def test_gru_sequence_bf16_against_the_float64_emulation(ops, monkeypatch, measu
     gi, w, masks, d_out, (out64, dgi64, dw64, min_pre) = sequence_case(shape, af, with_masks)
     if af == "relu":
         assert min_pre >= 0.05, min_pre
-    seen, bmms = [], []
-    inner, bmm = ops._launch, torch.bmm
-    monkeypatch.setattr(ops, "_launch", lambda name, s, *a, **k: (seen.append(name), inner(name, s, *a, **k))[1])
-    monkeypatch.setattr(torch, "bmm", lambda *a, **k: (bmms.append(1), bmm(*a, **k))[1])
-    got = run_sequence(ops, gi, w, masks, d_out, af, BF)
-    monkeypatch.setattr(ops, "_launch", inner)
-    monkeypatch.setattr(torch, "bmm", bmm)
+    bmms, bmm = [], torch.bmm
+    with monkeypatch.context() as m:
+        launches = spy_launches(m, ops)
+        m.setattr(torch, "bmm", lambda *a, **k: (bmms.append(1), bmm(*a, **k))[1])
+        got = run_sequence(ops, gi, w, masks, d_out, af, BF)
+    seen = [name for name, _ in launches]
     assert seen.count("gru_gemm_bf16") == 2 * (T - 1), seen
     assert seen.count("gru_gates_fwd_bf16") == T and seen.count("gru_gates_bwd_bf16") == T and seen.count("gemm_bf16_tn") == 3, seen
     assert not bmms and not {"gemm_nt_split_batched", "gemm_tn_split", "grouped_gemm", "grouped_gemm_split", "gru_gates_fwd", "gru_gates_bwd"} & set(seen), seen

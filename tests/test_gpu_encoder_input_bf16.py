@@ -20,7 +20,7 @@ import pytest
 import torch
 
 from kernel_harness import (BF, E_BADARG, E_UNSUPPORTED, SENT, WorstBar as Bars, _ptr, _same_bits, _sentinel, _untouched, dev,
-                            ops)  # noqa: F401  (ops: the fixture)
+                            ops, spy_launches)  # noqa: F401  (ops: the fixture)
 
 gpu = pytest.mark.gpu
 RTOL_MID = 2e-2
@@ -431,13 +431,11 @@ def run_fn(ops, table, ids, mx, w, b, d_gi, dense=False):
 def test_encoder_input_bf16_against_the_float64_emulation(ops, monkeypatch, measured, shape, with_masks):
     B, T, K, H, V = shape
     table, ids, mx, w, b, d_gi, want = fn_case(shape, with_masks)
-    seen, bmms = [], []
-    inner, bmm = ops._launch, torch.bmm
-    monkeypatch.setattr(ops, "_launch", lambda name, s, *a, **k: (seen.append((name, tuple(s))), inner(name, s, *a, **k))[1])
-    monkeypatch.setattr(torch, "bmm", lambda *a, **k: (bmms.append(1), bmm(*a, **k))[1])
-    got = run_fn(ops, table, ids, mx, w, b, d_gi)
-    monkeypatch.setattr(ops, "_launch", inner)
-    monkeypatch.setattr(torch, "bmm", bmm)
+    bmms, bmm = [], torch.bmm
+    with monkeypatch.context() as m:
+        seen = spy_launches(m, ops)
+        m.setattr(torch, "bmm", lambda *a, **k: (bmms.append(1), bmm(*a, **k))[1])
+        got = run_fn(ops, table, ids, mx, w, b, d_gi)
     names = [n for n, _ in seen]
     assert names.count("embed_pack_bf16") == 1 and names.count("gemm_bf16_nt_f32_bias") == 1 and names.count("embed_grad") == 1, seen
     assert names.count("gemm_bf16_tn") == 3 and names.count("gru_gemm_bf16") == 1 and names.count("column_sum") == 3, seen

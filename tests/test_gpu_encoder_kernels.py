@@ -19,7 +19,7 @@ import pytest
 import torch
 
 from kernel_harness import (EPS32, E_BADARG, E_UNSUPPORTED, INF, NAN, SENT, _bits, _ptr, _same_bits, _sentinel, _untouched, dev,
-                            ops)  # noqa: F401  (ops: the fixture)
+                            ops, spy_launches)  # noqa: F401  (ops: the fixture)
 from vqa_playground_pytorch_amd.encoder import BayesianGRU
 
 gpu = pytest.mark.gpu
@@ -805,15 +805,13 @@ def _sequence_case(ops, monkeypatch, measured, B, T, K, H, af, train, tag):
     lengths = torch.randint(1, T + 1, (B,), generator=gen)
     gy = torch.randn(B, H, generator=gen)
     x64, x32, xg = x.double().requires_grad_(), x.clone().requires_grad_(), x.clone().to(dev()).requires_grad_()
-    seen, bmms = [], []
-    inner, bmm = ops._launch, torch.bmm
-    monkeypatch.setattr(ops, "_launch", lambda name, shape, *a, **k: (seen.append((name, shape)), inner(name, shape, *a, **k))[1])
-    monkeypatch.setattr(torch, "bmm", lambda *a, **k: (bmms.append(tuple(a[0].shape) + tuple(a[1].shape)), bmm(*a, **k))[1])
-    yg = g32(xg, lengths.to(dev()))
-    yg.backward(gy.to(dev()))
-    torch.cuda.synchronize()
-    monkeypatch.setattr(ops, "_launch", inner)
-    monkeypatch.setattr(torch, "bmm", bmm)
+    bmms, bmm = [], torch.bmm
+    with monkeypatch.context() as m:
+        seen = spy_launches(m, ops)
+        m.setattr(torch, "bmm", lambda *a, **k: (bmms.append(tuple(a[0].shape) + tuple(a[1].shape)), bmm(*a, **k))[1])
+        yg = g32(xg, lengths.to(dev()))
+        yg.backward(gy.to(dev()))
+        torch.cuda.synchronize()
     y64 = c64(x64, lengths)
     y64.backward(gy.double())
     y32 = c32(x32, lengths)
@@ -913,11 +911,11 @@ def test_gru_sequence_issues_the_recorded_launches_in_order(ops, monkeypatch, ca
     gi = (0.5 * torch.randn(3, B, T, H, generator=gen)).to(dev()).requires_grad_()
     w = (torch.randn(3, H, H, generator=gen) / H ** 0.5).to(dev()).requires_grad_()
     masks = ((torch.rand(3, B, H, generator=gen) > 0.25).float() / 0.75).to(dev())
-    seen, inner = [], ops._launch
-    monkeypatch.setattr(ops, "_launch", lambda name, shape, *a, **k: (seen.append(name), inner(name, shape, *a, **k))[1])
-    out = ops.gru_sequence(gi, w, masks, "relu", compute_dtype=dtype)
-    out.backward(torch.randn(T, B, H, generator=gen).to(dev()))
-    torch.cuda.synchronize()
-    monkeypatch.setattr(ops, "_launch", inner)
+    with monkeypatch.context() as m:
+        launches = spy_launches(m, ops)
+        out = ops.gru_sequence(gi, w, masks, "relu", compute_dtype=dtype)
+        out.backward(torch.randn(T, B, H, generator=gen).to(dev()))
+        torch.cuda.synchronize()
+    seen = [name for name, _ in launches]
     assert seen == GRU_LAUNCHES[case], seen
     assert all(bool(torch.isfinite(t).all()) for t in (out, gi.grad, w.grad))

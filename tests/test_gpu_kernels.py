@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from kernel_harness import dev
+from kernel_harness import dev, spy_launches
 from oracle import kernels_np as K
 from oracle import seeded
 
@@ -224,8 +224,7 @@ def test_softmax_attention_pool_wrappers_keep_their_entry_points(ops, monkeypatc
     logits = 2.0 * seeded.seeded_array((B, N, G), 251)
     v = seeded.seeded_array((B, N, D), 252)
     gp, ga = g(seeded.seeded_array((B, G, D), 253)), g(seeded.seeded_array((B, N, G), 254))
-    seen, inner = [], ops._launch
-    monkeypatch.setattr(ops, "_launch", lambda name, shape, *a, **k: (seen.append((name, shape)), inner(name, shape, *a, **k))[1])
+    seen = spy_launches(monkeypatch, ops)
     got = {}
     for wrapper in ("plain", "drop"):
         lt, vt = g(logits, True), g(v).to(dtype).requires_grad_()
@@ -235,7 +234,6 @@ def test_softmax_attention_pool_wrappers_keep_their_entry_points(ops, monkeypatc
         ((pooled * gp).sum() + (alpha * ga).sum()).backward()
         got[wrapper] = (alpha.detach(), pooled.detach(), lt.grad, vt.grad)
     torch.cuda.synchronize()
-    monkeypatch.setattr(ops, "_launch", inner)
     assert seen == [("softmax_attention_pool_fwd" + sfx, (B, N, D, G)), ("softmax_attention_pool_bwd" + sfx, (B, N, D, G, True)),
                     ("softmax_attention_pool_drop_fwd" + sfx, (B, N, D, G)), ("softmax_attention_pool_drop_bwd" + sfx, (B, N, D, G, True))], seen
     for name, a, b in zip(("alpha", "pooled", "d_logits", "d_v"), got["plain"], got["drop"]):

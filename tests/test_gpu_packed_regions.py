@@ -19,7 +19,7 @@ import torch
 from oracle import reference_faithful as RF
 from oracle import seeded
 from kernel_harness import (BF, E_BADARG, E_UNSUPPORTED, F32, NAN, PAD, _bits, _call, _ceil, _out, _ptr, _same_bits, _untouched, _win,
-                            dev, ops)  # noqa: F401  (ops: the fixture)
+                            dev, ops, spy_launches)  # noqa: F401  (ops: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -272,13 +272,12 @@ PARENT_LAUNCHES = {False: _PARENT_UNMASKED, True: [_K3_MASKED.get(name, name) fo
 def _launch_names(monkeypatch, sample, a):
     from vqa_playground_pytorch_amd import CoR2Model, ops as o
     model = seeded.load_state(CoR2Model(["PAD", "UNK"], 300), 0).train().to(dev())
-    names, real = [], o._launch
-    monkeypatch.setattr(o, "_launch", lambda name, *rest: (names.append(name), real(name, *rest))[1])
-    torch.manual_seed(5)
-    RF.kld_sum_loss(model(sample), a).backward()
-    torch.cuda.synchronize()
-    monkeypatch.setattr(o, "_launch", real)
-    return names
+    with monkeypatch.context() as m:
+        seen = spy_launches(m, o)
+        torch.manual_seed(5)
+        RF.kld_sum_loss(model(sample), a).backward()
+        torch.cuda.synchronize()
+    return [name for name, _ in seen]
 
 
 def test_a_padded_batch_launches_what_it_launched_before(monkeypatch):

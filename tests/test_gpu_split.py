@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from kernel_harness import dev, ops  # noqa: F401  (ops: the fixture)
+from kernel_harness import dev, ops, spy_launches  # noqa: F401  (ops: the fixture)
 from oracle import kernels_np as K
 from oracle import seeded
 
@@ -332,14 +332,12 @@ def _relation_run(ops, monkeypatch, fused, v, t, c2, w, b, gy, p, seed, pregated
     monkeypatch.setenv("VQA_F32_PRODUCTS", "split")
     monkeypatch.setenv("VQA_RELATION_FUSED", "1" if fused else "0")
     tt, ct, wt, bt = (z.clone().requires_grad_(True) for z in (t, c2, w, b))
-    seen = []
-    inner = ops._launch
-    monkeypatch.setattr(ops, "_launch", lambda name, *a, **k: (seen.append(name), inner(name, *a, **k))[1])
-    y = ops.relation_projection(v, tt, ct, wt, bt, p, seed, pregated)
-    g = gy * (y.detach() > 0) if pregated else gy
-    y.backward(g)
-    monkeypatch.setattr(ops, "_launch", inner)
-    return y.detach(), {"d_t": tt.grad, "d_c2": ct.grad, "d_w": wt.grad, "d_b": bt.grad}, seen
+    with monkeypatch.context() as m:
+        seen = spy_launches(m, ops)
+        y = ops.relation_projection(v, tt, ct, wt, bt, p, seed, pregated)
+        g = gy * (y.detach() > 0) if pregated else gy
+        y.backward(g)
+    return y.detach(), {"d_t": tt.grad, "d_c2": ct.grad, "d_w": wt.grad, "d_b": bt.grad}, [name for name, _ in seen]
 
 
 @pytest.mark.parametrize("B,N,D,L,p,pregated", [(64, 36, 2048, 310, 0.5, False), (64, 36, 2048, 310, 0.0, True), (33, 36, 256, 310, 0.5, True),

@@ -1,10 +1,13 @@
 """tests/kernel_harness.py on the CPU: every guard the kernel tests lean on fails when it should.  Buffers are built with torch.full
 where the harness would allocate on the GPU; the Bars cases use dyadic numbers, so every comparison below is exact."""
+import ctypes
+
 import pytest
 import torch
 
 from kernel_harness import (BF, EPS32, F32, F64, INF, NAN, PAD, SENT, Bars, WorstBar, _in_host, _same_bits, _take, _untouched, _win,
-                            assert_exact, launch_sites, spell)
+                            assert_exact, check_args, forbid_launches, launch_sites, spell, spy_launches)
+from vqa_playground_pytorch_amd import _lib
 
 fails = pytest.raises(AssertionError)
 
@@ -205,3 +208,69 @@ def test_in_pads_with_nan_and_refuses_what_fp32_cannot_hold():
         _in_host(torch.tensor([[1.0, 1.0 + 2.0 ** -30]], dtype=F64))
     with pytest.raises(AssertionError, match="not exact in fp32"):
         _in_host(torch.tensor([[2 ** 24 + 1]]))
+
+
+# ---- the argument check of _call ---------------------------------------------------------------------------------------------
+class _Bound:
+    """a stand-in for a bound entry point: its name and the header's argument types, never called"""
+
+    def __init__(self, name):
+        self.__name__, self.argtypes = name, _lib.SIGNATURES[name][1]
+
+
+def test_call_checks_its_arguments_against_the_bound_signature():
+    fn = _Bound("vqa_softmax_attention_pool_len_fwd")     # (logits, v, lens, alpha, pooled, first, p_drop, seed, seed_ptr, B, N, D, G, stream)
+    p, words = ctypes.c_void_p(4096), (ctypes.c_uint64 * 1)()
+    good = [p, p, p, p, p, None, 0.5, 7, words, 2, 36, 64, 4, ctypes.c_void_p(0)]
+    check_args(fn, good)
+    check_args(fn, good[:6] + [0, 2 ** 40, ctypes.byref(words), 2, 36, 64, 4, None])
+    check_args(fn, [ctypes.pointer(words)] + good[1:])
+
+    def bad(at, value, message):
+        args = list(good)
+        args[at] = value
+        with pytest.raises(AssertionError, match=message):
+            check_args(fn, args)
+
+    bad(2, 36, r"argument 3 \(`lens`\) of vqa_softmax_attention_pool_len_fwd takes a pointer, got int 36")
+    bad(0, 0.5, r"argument 1 \(`logits`\) of .* takes a pointer, got float 0.5")
+    bad(5, False, r"argument 6 \(`first`\) of .* takes a pointer, got bool False")
+    bad(1, torch.zeros(2), r"argument 2 \(`v`\) of .* takes a pointer, got Tensor")
+    bad(13, 0, r"argument 14 \(`stream`\) of .* takes a pointer, got int 0")
+    bad(9, torch.tensor(2), r"argument 10 \(`B`\) of .* takes an integer, got Tensor")
+    bad(10, 36.0, r"argument 11 \(`N`\) of .* takes an integer, got float 36.0")
+    bad(11, True, r"argument 12 \(`D`\) of .* takes an integer, got bool True")
+    bad(7, p, r"argument 8 \(`seed`\) of .* takes an integer, got c_void_p")
+    bad(6, None, r"argument 7 \(`p_drop`\) of .* takes a number, got NoneType")
+    bad(6, torch.tensor(0.5), r"argument 7 \(`p_drop`\) of .* takes a number, got Tensor")
+    for args in (good[:-1], good + [None], good[:9] + good[10:]):
+        with pytest.raises(AssertionError, match=r"vqa_softmax_attention_pool_len_fwd takes 14 arguments \(logits, v, lens, .*, stream\), got %d" % len(args)):
+            check_args(fn, args)
+    check_args(_Bound("vqa_rmsprop_step"), [p, p, p, 10, None, 0.1, 0.99, 1e-8, None])
+    with pytest.raises(AssertionError, match=r"argument 7 \(`alpha`\) of vqa_rmsprop_step takes a number, got c_void_p"):
+        check_args(_Bound("vqa_rmsprop_step"), [p, p, p, 10, None, 0.1, p, 1e-8, None])
+
+
+# ---- ops._launch, watched or forbidden ---------------------------------------------------------------------------------------
+class _Ops:
+    def __init__(self):
+        self.calls = []
+        self._launch = lambda name, shape, fn, *args: self.calls.append((name, shape, fn, args)) or 7
+
+
+def test_spy_launches_records_and_forwards(monkeypatch):
+    ops = _Ops()
+    with monkeypatch.context() as m:
+        seen = spy_launches(m, ops)
+        assert ops._launch("a", (1, 2), len, 3, 4) == 7 and ops._launch("b", (), None) == 7
+    ops._launch("c", (5,), None)
+    assert seen == [("a", (1, 2)), ("b", ())]
+    assert ops.calls == [("a", (1, 2), len, (3, 4)), ("b", (), None, ()), ("c", (5,), None, ())]
+
+
+def test_forbid_launches_fails_the_test_that_launches(monkeypatch):
+    ops = _Ops()
+    forbid_launches(monkeypatch, ops)
+    with pytest.raises(pytest.fail.Exception, match="a kernel was launched"):
+        ops._launch("a", (1,), None)
+    assert ops.calls == []

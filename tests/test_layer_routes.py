@@ -11,6 +11,7 @@ Below the table: the front that cor2.Model and oda.Model share (layers.RegionQue
 import pytest
 import torch
 
+from kernel_harness import forbid_launches
 from vqa_playground_pytorch_amd import CoR2Model, ODAModel, layers, ops
 from vqa_playground_pytorch_amd.layers import MyConv1d
 
@@ -294,7 +295,7 @@ def _sample(B=3, regions=36, **more):
 @pytest.mark.parametrize("cls,kw", MODELS, ids=["cor2", "oda"])
 def test_v_len_refusals(cls, kw, monkeypatch):
     """wrong rank, wrong length, not a tensor, not integers, out of range -- each a ValueError before any layer runs"""
-    monkeypatch.setattr(ops, "_launch", lambda *a, **k: pytest.fail("a kernel was launched"))
+    forbid_launches(monkeypatch, ops)
     model = cls(["PAD", "UNK"], 20, **kw).eval()
     monkeypatch.setattr(model.compress_v, "forward", lambda *a, **k: pytest.fail("a layer ran"))
     i32 = torch.int32

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_harness import forbid_launches
 from vqa_playground_pytorch_amd import CoR2Model, ODAModel, _lib, feed, ops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -251,7 +252,7 @@ def _packed_sample(B=3, regions=36):
 
 
 def test_models_refuse_malformed_packed_batches_before_anything_runs(monkeypatch):
-    monkeypatch.setattr(ops, "_launch", lambda *a, **k: pytest.fail("a kernel was launched"))
+    forbid_launches(monkeypatch, ops)
     model = CoR2Model(["PAD", "UNK"], 50).eval()
     monkeypatch.setattr(model.compress_v, "forward", lambda *a, **k: pytest.fail("a layer ran"))
     s = _packed_sample()

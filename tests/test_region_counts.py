@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_harness import forbid_launches
 from vqa_playground_pytorch_amd import CoR2Model, ODAModel, _lib, feed
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -140,7 +141,7 @@ def _sample(B=3, regions=36):
 def test_cor2_refuses_host_counts_outside_1_to_n_before_anything_runs(bad, dtype, monkeypatch):
     """the validation sits in front of every layer: with all of ops' launches made to fail the ValueError still comes first"""
     from vqa_playground_pytorch_amd import ops
-    monkeypatch.setattr(ops, "_launch", lambda *a, **k: pytest.fail("a kernel was launched"))
+    forbid_launches(monkeypatch, ops)
     model = CoR2Model(["PAD", "UNK"], 50).eval()
     monkeypatch.setattr(model.compress_v, "forward", lambda *a, **k: pytest.fail("a layer ran"))
     with pytest.raises(ValueError, match="1..36"):

@@ -16,7 +16,6 @@ the producing layer's activation / dropout gradient -- it holds the producer's s
 so the producer's backward starts at its GEMMs.  Activations that feed a dropout layer are stored dropped out (0 or
 x/(1-p)), like K3 stores the pooled glimpses: "stored value > 0" is then "kept and active".
 """
-import ctypes
 import heapq
 import math
 import os
@@ -25,34 +24,15 @@ import torch
 
 from . import _lib, ops
 
-_c = ctypes
-MAX_GROUP = 24          # epilogue jobs per launch (VQA_GROUPED_MAX)
-MAX_GEMMS = 16          # GEMM problems per launch (VQA_GROUPED_GEMM_MAX)
-
-
-class GemmProblem(_c.Structure):          # VqaGemmProblem (include/vqa_mi355x.h)
-    _fields_ = [("A", _c.c_void_p), ("B", _c.c_void_p), ("slab", _c.c_void_p), ("colsum", _c.c_void_p),
-                ("slab_stride", _c.c_longlong), ("lda", _c.c_int), ("ldb", _c.c_int), ("M", _c.c_int), ("N", _c.c_int),
-                ("K", _c.c_int), ("form", _c.c_int), ("ksplit", _c.c_int), ("slab_base", _c.c_int), ("Ka", _c.c_int),
-                ("Kb", _c.c_int), ("Ma", _c.c_int), ("Nb", _c.c_int),
-                # direct output (the tile is finished in the GEMM kernel; no slab, no epilogue job)
-                ("out", _c.c_void_p), ("colsum_out", _c.c_void_p), ("bias", _c.c_void_p), ("gate_y", _c.c_void_p),
-                ("seed_ptr", _c.c_void_p), ("seed", _c.c_uint64), ("ldo", _c.c_int), ("ld_gate", _c.c_int), ("act", _c.c_int),
-                ("gate", _c.c_int), ("drop_base", _c.c_uint32), ("drop_ld", _c.c_uint32), ("p_drop", _c.c_float),
-                ("gate_scale", _c.c_float)]
-
-
-class EpilogueJob(_c.Structure):          # VqaEpilogueJob
-    _fields_ = [("slab", _c.c_void_p), ("bias", _c.c_void_p), ("aux", _c.c_void_p), ("aux2", _c.c_void_p),
-                ("out", _c.c_void_p), ("out2", _c.c_void_p), ("seed_ptr", _c.c_void_p), ("seed", _c.c_uint64),
-                ("slab_stride", _c.c_longlong), ("S", _c.c_int), ("M", _c.c_int), ("N", _c.c_int), ("kind", _c.c_int),
-                ("ldo", _c.c_int), ("ld_aux", _c.c_int), ("act", _c.c_int), ("gate", _c.c_int), ("R", _c.c_int),
-                ("seg", _c.c_int), ("seg_ld", _c.c_int), ("drop_base", _c.c_uint32), ("drop_ld", _c.c_uint32),
-                ("p_drop", _c.c_float), ("gate_scale", _c.c_float)]
-
+# the header's own (include/vqa_mi355x.h): the launch limits, the two table records, the epilogue kinds
+MAX_GROUP = _lib.DEFINES["VQA_GROUPED_MAX"]            # epilogue jobs per launch
+MAX_GEMMS = _lib.DEFINES["VQA_GROUPED_GEMM_MAX"]       # GEMM problems per launch
+GemmProblem = _lib.STRUCTS["VqaGemmProblem"]
+EpilogueJob = _lib.STRUCTS["VqaEpilogueJob"]
+EPI_SUM, EPI_LINEAR, EPI_RANK_PRODUCT, EPI_GRAD, EPI_RANK_PRODUCT_BWD = (
+    _lib.DEFINES["VQA_EPI_" + k] for k in ("SUM", "LINEAR", "RANK_PRODUCT", "GRAD", "RANK_PRODUCT_BWD"))
 
 NT, NN, TN, NN_A4, TN_A4 = 0, 1, 2, 3, 4
-EPI_SUM, EPI_LINEAR, EPI_RANK_PRODUCT, EPI_GRAD, EPI_RANK_PRODUCT_BWD = 0, 1, 2, 3, 4
 ACT = {None: 0, "": 0, "relu": 1, "sigmoid": 2}
 
 # VQA_HEAD: which of a model's [B,.]-sized layers run as grouped phases.

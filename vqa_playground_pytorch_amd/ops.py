@@ -60,10 +60,11 @@ def _launch(name, shape, fn, *args):
         b.record()
         t.events.setdefault((name, shape), []).append((a, b))
         if (name, shape) not in t.grids:      # the device kernels behind this call: grid sizes in work-items, launch order
-            buf = (ctypes.c_ulonglong * 16)()
-            n = handle.vqa_launch_log(buf, 16)
+            cap = _lib.DEFINES["VQA_LAUNCH_LOG_CAP"]
+            buf = (ctypes.c_ulonglong * cap)()
+            n = handle.vqa_launch_log(buf, cap)
             t.grids[(name, shape)] = tuple((int(buf[i]), (handle.vqa_launch_log_kernel(i) or b"").decode())
-                                           for i in range(min(n, 16)))
+                                           for i in range(min(n, cap)))
     else:
         rc = fn(*args, _stream())
     _lib.check(rc, name)
@@ -631,7 +632,7 @@ def _shadow(master, shape, tag, dtype=torch.bfloat16):
     return buf
 
 
-PACK_BLOCK = 1024      # VQA_PACK_BLOCK (include/vqa_mi355x.h)
+PACK_BLOCK = _lib.DEFINES["VQA_PACK_BLOCK"]
 
 
 class ShadowPlan:
