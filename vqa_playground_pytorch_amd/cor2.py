@@ -15,7 +15,7 @@ from .layers import MutanFusion, MyATT, MyConv1d, MyLinear, RegionQuestionModel,
 
 class Model(RegionQuestionModel):
     def __init__(self, vocab_words=None, num_ans=None, seq2vec=None, relation_mode=1, compute_dtype=None, encoder_dtype=None,
-                 encoder_input_dtype=None):
+                 encoder_input_dtype=None, encoder_length_aware=None):
         super().__init__()
         self.vocab_words = vocab_words
         self.num_classes = num_ans
@@ -30,7 +30,7 @@ class Model(RegionQuestionModel):
         # 0 = pairwise (every (i,j) term summed from the LDS tile), 1 = factored (same value, one pass)
         self.relation_mode = relation_mode
 
-        self._set_seq2vec(seq2vec, vocab_words, encoder_dtype, encoder_input_dtype)
+        self._set_seq2vec(seq2vec, vocab_words, encoder_dtype, encoder_input_dtype, encoder_length_aware)
         self.compress_v = MyConv1d(2048, 310, 1, 1, p=0.5, af="relu")
         self.compress_v2 = MyConv1d(2048, 310, 1, 1, p=0.5, af="relu")
         self.compress_q = MyLinear(2400, 310, p=0.5, af="relu")

@@ -45,9 +45,13 @@ struct GruBfArgs {
   int ldc;
   int M, N, Kp;          // Kp: the contraction rounded up to a multiple of 64 (the operand rows' zero pads)
   int tiles_m, tiles_n;
+  const int* lens;       // LEN instantiations only: [M] rows' step counts (device), and the step `t` of this launch
+  int t;
 };
 
-template <int BM, int BN>
+// LEN (vqa_gru_gemm_bf16_len): a workgroup whose row tile holds no row with lens[row] > t returns before the tile loop and writes
+// nothing -- one workgroup-uniform vote, ahead of every LDS use and every other barrier.
+template <int BM, int BN, bool LEN = false>
 __global__ __launch_bounds__(kBfThreads) void gru_gemm_bf16_kernel(GruBfArgs q) {
   using T = BfTile<BM, BN>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -55,6 +59,11 @@ __global__ __launch_bounds__(kBfThreads) void gru_gemm_bf16_kernel(GruBfArgs q) 
   const int lin = xcd_remap(blockIdx.x, gridDim.x);
   const int prob = __builtin_amdgcn_readfirstlane(lin / tiles), tile = lin - prob * tiles;
   const int m0 = (tile % q.tiles_m) * BM, n0 = (tile / q.tiles_m) * BN;
+  if constexpr (LEN) {
+    int live = 0;
+    for (int i = threadIdx.x; i < BM; i += kBfThreads) live |= (m0 + i < q.M && q.lens[m0 + i] > q.t) ? 1 : 0;
+    if (!__syncthreads_or(live)) return;
+  }
   const bf16* A = q.a + (size_t)prob * q.a_gs;
   const bf16* W = q.w + (size_t)prob * q.w_gs;
   float* C = q.c + (size_t)prob * q.c_gs;
@@ -171,17 +180,41 @@ static int gru_bf16_check(const char* who, const void* hist, size_t hist_gs, int
   return VQA_OK;
 }
 
-template <int BM, int BN>
+template <int BM, int BN, bool LEN = false>
 static int launch_gru_gemm_bf16(GruBfArgs q, int G, hipStream_t s) {
   q.tiles_m = (q.M + BM - 1) / BM;
   q.tiles_n = (q.N + BN - 1) / BN;
   const size_t lds = BfTile<BM, BN>::kSmemBytes;
-  VQA_ENSURE_LDS((gru_gemm_bf16_kernel<BM, BN>), lds);
-  VQA_LAUNCH((gru_gemm_bf16_kernel<BM, BN>), dim3(q.tiles_m * q.tiles_n * G), dim3(kBfThreads), lds, s, q);
-  return check_launch("gru_gemm_bf16");
+  if constexpr (LEN) {
+    VQA_ENSURE_LDS((gru_gemm_bf16_kernel<BM, BN, true>), lds);
+    VQA_LAUNCH((gru_gemm_bf16_kernel<BM, BN, true>), dim3(q.tiles_m * q.tiles_n * G), dim3(kBfThreads), lds, s, q);
+    return check_launch("gru_gemm_bf16_len");
+  } else {
+    VQA_ENSURE_LDS((gru_gemm_bf16_kernel<BM, BN>), lds);
+    VQA_LAUNCH((gru_gemm_bf16_kernel<BM, BN>), dim3(q.tiles_m * q.tiles_n * G), dim3(kBfThreads), lds, s, q);
+    return check_launch("gru_gemm_bf16");
+  }
 }
 
 static int padded64(int K) { return (K + 63) / 64 * 64; }
+
+static int gru_gemm_bf16_any(const char* who, bool len, const vqa_bf16_t* a, long a_gs, int lda, const vqa_bf16_t* w, long w_gs, int ldw,
+                             float* c, long c_gs, int ldc, int G, int M, int N, int K, const int* lens, int t, hipStream_t s) {
+  VQA_REQUIRE(a && w && c && (!len || lens), VQA_E_BADARG, "%s: null pointer", who);
+  VQA_REQUIRE(G >= 1 && G <= 4096 && M >= 1 && N >= 1 && K >= 1 && a_gs >= 0 && w_gs >= 0 && c_gs >= 0, VQA_E_BADARG,
+              "%s: bad sizes G=%d M=%d N=%d K=%d", who, G, M, N, K);
+  VQA_REQUIRE(vqa_gru_gemm_bf16_supported(M, N, K, lda, ldw, ldc) == 1, VQA_E_UNSUPPORTED,
+              "%s: shape outside the kernel (M=%d N=%d K=%d lda=%d ldw=%d ldc=%d): N %% 8 == 0, K %% 8 == 0, operand rows "
+              "padded to a multiple of 64 elements (lda, ldw >= K rounded up to 64, %% 8 == 0), ldc >= N",
+              who, M, N, K, lda, ldw, ldc);
+  VQA_REQUIRE(aligned(a, 16) && aligned(w, 16) && aligned(c, 4) && a_gs % 8 == 0 && w_gs % 8 == 0, VQA_E_UNSUPPORTED,
+              "%s: a, w (and their problem strides) must be 16-byte aligned", who);
+  const GruBfArgs q{reinterpret_cast<const bf16*>(a), a_gs, lda, reinterpret_cast<const bf16*>(w), w_gs, ldw, c, c_gs, ldc,
+                    M, N, padded64(K), 0, 0, lens, t};
+  if (len) return M <= 64 ? launch_gru_gemm_bf16<64, 128, true>(q, G, s) : launch_gru_gemm_bf16<128, 128, true>(q, G, s);
+  if (M <= 64) return launch_gru_gemm_bf16<64, 128>(q, G, s);
+  return launch_gru_gemm_bf16<128, 128>(q, G, s);
+}
 
 }  // namespace vqa
 
@@ -196,21 +229,17 @@ extern "C" int vqa_gru_gemm_bf16_supported(int M, int N, int K, int lda, int ldw
 
 extern "C" int vqa_gru_gemm_bf16(const vqa_bf16_t* a, long a_gs, int lda, const vqa_bf16_t* w, long w_gs, int ldw, float* c,
                                  long c_gs, int ldc, int G, int M, int N, int K, vqa_stream_t stream) {
-  VQA_REQUIRE(a && w && c, VQA_E_BADARG, "gru_gemm_bf16: null pointer");
-  VQA_REQUIRE(G >= 1 && G <= 4096 && M >= 1 && N >= 1 && K >= 1 && a_gs >= 0 && w_gs >= 0 && c_gs >= 0, VQA_E_BADARG,
-              "gru_gemm_bf16: bad sizes G=%d M=%d N=%d K=%d", G, M, N, K);
-  VQA_REQUIRE(vqa_gru_gemm_bf16_supported(M, N, K, lda, ldw, ldc) == 1, VQA_E_UNSUPPORTED,
-              "gru_gemm_bf16: shape outside the kernel (M=%d N=%d K=%d lda=%d ldw=%d ldc=%d): N %% 8 == 0, K %% 8 == 0, operand rows "
-              "padded to a multiple of 64 elements (lda, ldw >= K rounded up to 64, %% 8 == 0), ldc >= N",
-              M, N, K, lda, ldw, ldc);
-  VQA_REQUIRE(aligned(a, 16) && aligned(w, 16) && aligned(c, 4) && a_gs % 8 == 0 && w_gs % 8 == 0, VQA_E_UNSUPPORTED,
-              "gru_gemm_bf16: a, w (and their problem strides) must be 16-byte aligned");
-  const GruBfArgs q{reinterpret_cast<const bf16*>(a), a_gs, lda, reinterpret_cast<const bf16*>(w), w_gs, ldw, c, c_gs, ldc,
-                    M, N, padded64(K), 0, 0};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (M <= 64) return launch_gru_gemm_bf16<64, 128>(q, G, s);
-  return launch_gru_gemm_bf16<128, 128>(q, G, s);
+  return gru_gemm_bf16_any("gru_gemm_bf16", false, a, a_gs, lda, w, w_gs, ldw, c, c_gs, ldc, G, M, N, K, nullptr, 0,
+                           static_cast<hipStream_t>(stream));
 }
+
+extern "C" int vqa_gru_gemm_bf16_len(const vqa_bf16_t* a, long a_gs, int lda, const vqa_bf16_t* w, long w_gs, int ldw, float* c,
+                                     long c_gs, int ldc, int G, int M, int N, int K, const int32_t* lens, int t, vqa_stream_t stream) {
+  return gru_gemm_bf16_any("gru_gemm_bf16_len", true, a, a_gs, lda, w, w_gs, ldw, c, c_gs, ldc, G, M, N, K, lens, t,
+                           static_cast<hipStream_t>(stream));
+}
+
+extern "C" int vqa_gru_gemm_bf16_tile_rows(int M) { return M <= 64 ? 64 : 128; }
 
 extern "C" int vqa_gru_gates_fwd_bf16(const float* gi, const float* a, const float* h_prev, const float* masks, float* h_new,
                                       vqa_bf16_t* hm_next, size_t hist_group_stride, int ld, float* r_s, float* i_s, float* n_s,

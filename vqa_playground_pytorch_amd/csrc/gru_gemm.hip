@@ -65,9 +65,14 @@ struct BatchNtArgs {
   const float* Bf;      // the fp32 weights (repair path): B_g[n][k] = Bf[g * bf_gs + n * bf_sn + k * bf_sk]
   long bf_gs;
   int bf_sn, bf_sk;
+  const int* lens;      // LEN instantiations only: [M] rows' step counts (device), and the step `t` of this launch
+  int t;
 };
 
-template <int RB, int CB, int NR>
+// LEN (vqa_gemm_nt_split_batched_len): a workgroup whose row tile holds no row with lens[row] > t returns before its main loop and
+// writes nothing -- one workgroup-uniform vote, ahead of every LDS use and every other barrier.  LEN = false compiles to the kernel
+// without the flag.
+template <int RB, int CB, int NR, bool LEN = false>
 __global__ __launch_bounds__(sp::kThreads, 1) void gemm_nt_batched_kernel(BatchNtArgs q) {
   using S = rt::NtShape<RB, CB, 1, 2, 2>;
   using sp::f32x4;
@@ -88,6 +93,11 @@ __global__ __launch_bounds__(sp::kThreads, 1) void gemm_nt_batched_kernel(BatchN
   const int tm = __builtin_amdgcn_readfirstlane(q.col_major ? tile % q.tiles_m : tile / q.tiles_n);
   const int tn = __builtin_amdgcn_readfirstlane(q.col_major ? tile / q.tiles_m : tile % q.tiles_n);
   const int m0 = tm * S::BM, n0 = tn * S::BN + wn * (16 * CB);
+  if constexpr (LEN) {
+    int live = 0;
+    for (int i = threadIdx.x; i < S::BM; i += sp::kThreads) live |= (m0 + i < q.M && q.lens[m0 + i] > q.t) ? 1 : 0;
+    if (!__syncthreads_or(live)) return;
+  }
   const int chunks = q.Kp / sp::kChunk;
 
   f32x4 acc[RB][CB];
@@ -179,16 +189,59 @@ static size_t r256(size_t b) { return (b + 255) & ~(size_t)255; }
 static int padded_k(int K) { return (K + 63) / 64 * 64; }
 static size_t image_bytes(int N, int K) { return ((sp::packed_bytes(N, padded_k(K)) + 255) & ~(size_t)255); }
 
-template <int RB, int NR>
+template <int RB, int NR, bool LEN = false>
 static int launch_batched(const BatchNtArgs& a, int G, hipStream_t s) {
   using S = rt::NtShape<RB, 5, 1, 2, 2>;
   BatchNtArgs q = a;
   q.tiles_m = (a.M + S::BM - 1) / S::BM;
   q.tiles_n = (a.N + S::BN - 1) / S::BN;
   q.col_major = vqa::option("VQA_GRU_GEMM_ORDER") ? (vqa::option_is("VQA_GRU_GEMM_ORDER", 'c') ? 1 : 0) : (q.tiles_m <= 8 ? 1 : 0);
-  VQA_ENSURE_LDS((gemm_nt_batched_kernel<RB, 5, NR>), S::kLdsBytes);
-  VQA_LAUNCH((gemm_nt_batched_kernel<RB, 5, NR>), dim3(q.tiles_m * q.tiles_n * G), dim3(sp::kThreads), S::kLdsBytes, s, q);
-  return check_launch("gemm_nt_split_batched");
+  if constexpr (LEN) {
+    VQA_ENSURE_LDS((gemm_nt_batched_kernel<RB, 5, NR, true>), S::kLdsBytes);
+    VQA_LAUNCH((gemm_nt_batched_kernel<RB, 5, NR, true>), dim3(q.tiles_m * q.tiles_n * G), dim3(sp::kThreads), S::kLdsBytes, s, q);
+    return check_launch("gemm_nt_split_batched_len");
+  } else {
+    VQA_ENSURE_LDS((gemm_nt_batched_kernel<RB, 5, NR>), S::kLdsBytes);
+    VQA_LAUNCH((gemm_nt_batched_kernel<RB, 5, NR>), dim3(q.tiles_m * q.tiles_n * G), dim3(sp::kThreads), S::kLdsBytes, s, q);
+    return check_launch("gemm_nt_split_batched");
+  }
+}
+
+// row blocks per workgroup: what leaves the fewest idle CUs in the last wave of workgroups (ties: the taller tile)
+static int batched_row_blocks(int G, int M, int N) {
+  int rb = 9;
+  if (const char* e = vqa::option("VQA_GRU_GEMM_RB")) rb = std::atoi(e);
+  else if (M <= 1024) {
+    double best = 1e30;
+    for (int cand : {9, 8, 7}) {
+      const long wgs = (long)((M + 16 * cand - 1) / (16 * cand)) * ((N + 159) / 160) * G;
+      const double cost = (double)((wgs + 255) / 256) * cand;      // waves of workgroups x time per workgroup
+      if (cost < best - 1e-9) best = cost, rb = cand;
+    }
+  }
+  return rb == 7 || rb == 8 ? rb : 9;
+}
+
+static int nt_batched(const char* who, bool len, const float* a, long a_gs, int lda, const void* image, float* c, long c_gs, int ldc,
+                      const float* bias, int bias_gs, const float* w, long w_gs, int w_sn, int w_sk, int G, int M, int N, int K,
+                      const int* lens, int t, hipStream_t s) {
+  VQA_REQUIRE(a && image && c && (!len || lens), VQA_E_BADARG, "%s: null pointer", who);
+  VQA_REQUIRE(G >= 1 && G <= 4096, VQA_E_BADARG, "%s: G out of range", who);
+  VQA_REQUIRE(vqa_gemm_nt_split_batched_supported(M, N, K, lda, ldc) == 1, VQA_E_UNSUPPORTED,
+              "%s: shape outside the engine (M=%d N=%d K=%d lda=%d ldc=%d): M >= 64, lda %% 4 == 0", who, M, N, K, lda, ldc);
+  VQA_REQUIRE(aligned(a, 16) && a_gs % 4 == 0 && aligned(image, 16), VQA_E_UNSUPPORTED,
+              "%s: a (and its batch stride) and the image must be 16-byte aligned", who);
+  BatchNtArgs q{a, a_gs, lda, static_cast<const sp::u32x4*>(image), image_bytes(N, K) / 16, c, c_gs, ldc, bias, bias_gs, M, N, padded_k(K), K,
+                0, 0, 0, w, w_gs, w_sn, w_sk, lens, t};
+  const int rb = batched_row_blocks(G, M, N);
+  if (len) {
+    if (rb == 7) return launch_batched<7, 7, true>(q, G, s);
+    if (rb == 8) return launch_batched<8, 4, true>(q, G, s);
+    return launch_batched<9, 3, true>(q, G, s);
+  }
+  if (rb == 7) return launch_batched<7, 7>(q, G, s);
+  if (rb == 8) return launch_batched<8, 4>(q, G, s);
+  return launch_batched<9, 3>(q, G, s);
 }
 
 }  // namespace vqa
@@ -222,30 +275,18 @@ extern "C" int vqa_gemm_nt_split_batched_supported(int M, int N, int K, int lda,
 extern "C" int vqa_gemm_nt_split_batched(const float* a, long a_gs, int lda, const void* image, float* c, long c_gs, int ldc,
                                          const float* bias, int bias_gs, const float* w, long w_gs, int w_sn, int w_sk, int G, int M,
                                          int N, int K, vqa_stream_t stream) {
-  VQA_REQUIRE(a && image && c, VQA_E_BADARG, "gemm_nt_split_batched: null pointer");
-  VQA_REQUIRE(G >= 1 && G <= 4096, VQA_E_BADARG, "gemm_nt_split_batched: G out of range");
-  VQA_REQUIRE(vqa_gemm_nt_split_batched_supported(M, N, K, lda, ldc) == 1, VQA_E_UNSUPPORTED,
-              "gemm_nt_split_batched: shape outside the engine (M=%d N=%d K=%d lda=%d ldc=%d): M >= 64, lda %% 4 == 0", M, N, K, lda, ldc);
-  VQA_REQUIRE(aligned(a, 16) && a_gs % 4 == 0 && aligned(image, 16), VQA_E_UNSUPPORTED,
-              "gemm_nt_split_batched: a (and its batch stride) and the image must be 16-byte aligned");
-  BatchNtArgs q{a, a_gs, lda, static_cast<const sp::u32x4*>(image), image_bytes(N, K) / 16, c, c_gs, ldc, bias, bias_gs, M, N, padded_k(K), K,
-                0, 0, 0, w, w_gs, w_sn, w_sk};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  // row blocks per workgroup: what leaves the fewest idle CUs in the last wave of workgroups (ties: the taller tile)
-  int rb = 9;
-  if (const char* e = vqa::option("VQA_GRU_GEMM_RB")) rb = std::atoi(e);
-  else if (M <= 1024) {
-    double best = 1e30;
-    for (int cand : {9, 8, 7}) {
-      const long wgs = (long)((M + 16 * cand - 1) / (16 * cand)) * ((N + 159) / 160) * G;
-      const double cost = (double)((wgs + 255) / 256) * cand;      // waves of workgroups x time per workgroup
-      if (cost < best - 1e-9) best = cost, rb = cand;
-    }
-  }
-  if (rb == 7) return launch_batched<7, 7>(q, G, s);
-  if (rb == 8) return launch_batched<8, 4>(q, G, s);
-  return launch_batched<9, 3>(q, G, s);
+  return nt_batched("gemm_nt_split_batched", false, a, a_gs, lda, image, c, c_gs, ldc, bias, bias_gs, w, w_gs, w_sn, w_sk, G, M, N, K,
+                    nullptr, 0, static_cast<hipStream_t>(stream));
 }
+
+extern "C" int vqa_gemm_nt_split_batched_len(const float* a, long a_gs, int lda, const void* image, float* c, long c_gs, int ldc,
+                                             const float* bias, int bias_gs, const float* w, long w_gs, int w_sn, int w_sk, int G,
+                                             int M, int N, int K, const int32_t* lens, int t, vqa_stream_t stream) {
+  return nt_batched("gemm_nt_split_batched_len", true, a, a_gs, lda, image, c, c_gs, ldc, bias, bias_gs, w, w_gs, w_sn, w_sk, G, M, N, K,
+                    lens, t, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int vqa_gemm_nt_split_batched_tile_rows(int G, int M, int N) { return 16 * batched_row_blocks(G, M, N); }
 
 extern "C" int vqa_gemm_tn_split_supported(int M, int N1, int N2, int ldg, int ldx) {
   return (M >= 1152 && N1 >= 16 && N1 % 2 == 0 && N2 >= 64 && N2 % 4 == 0 && ldg % 2 == 0 && ldg >= N1 && ldx % 4 == 0 && ldx >= N2 &&

@@ -61,8 +61,13 @@ class BayesianGRU(nn.Module):
     (SequentialDropout); ``forward(x [B,T,in], lengths [B]) -> [B,hidden]`` = the state at step lengths-1."""
 
     def __init__(self, input_size, hidden_size, bias_ih=True, bias_hh=False, dropout=0.25, return_last=True, af="tanh",
-                 compute_dtype=None, input_dtype=None):
+                 compute_dtype=None, input_dtype=None, length_aware=False):
         super().__init__()
+        # True: stop computing the time steps past each question's end (include/vqa_mi355x.h and INTEGRATION.md section 2 state
+        # the contract): row b runs steps t < L[b] as ever and keeps its state afterwards.  With return_last=True the returned
+        # vector and every gradient are the default's bit for bit; all_hiddens / the return_last=False output hold the last valid
+        # state past a question's end where the default, as the reference, lets it evolve over PAD embeddings -- hence a choice.
+        self.length_aware = bool(length_aware)
         # torch.bfloat16: the recurrent products in mixed precision (bf16 operands, fp32 accumulation; csrc/gru_bf16.hip states
         # the contract, INTEGRATION.md section 2).  Parameters, state and the input side stay fp32 either way.
         self.compute_dtype = ops.parse_compute_dtype(compute_dtype)
@@ -113,12 +118,24 @@ class BayesianGRU(nn.Module):
             gi = ops.encoder_input_bf16(table, x, mx, w_in, b_in, padding_idx)
         else:
             gi = ops.encoder_input_bf16(x, None, mx, w_in, b_in)
-        out = ops.gru_sequence(gi, ops.stack_params([m.weight for m in hid]), mh, self.af, self.compute_dtype)      # [T,B,H]
+        out = ops.gru_sequence(gi, ops.stack_params([m.weight for m in hid]), mh, self.af, self.compute_dtype,
+                               lens=self._steps(lengths, B, T, x.device))                                            # [T,B,H]
         if not self.return_last:
             return out.transpose(0, 1)
         self.all_hiddens = out.detach().transpose(0, 1)
         idx = (lengths.long() - 1) % T
         return out[idx, torch.arange(B, device=x.device)]
+
+    def _steps(self, lengths, B, T, device):
+        """The effective lengths L [B] of the length-aware mode (int32, on `device`; None when the mode is off): L[b] = len[b] if
+        1 <= len[b] <= T, else T -- the (len - 1) % T rule of the gather: an all-PAD question runs every step.  Torch ops only:
+        the host never reads it, a replayed graph recomputes it from the batch it is given."""
+        if not self.length_aware:
+            return None
+        if lengths is None:
+            return torch.full((B,), T, device=device, dtype=torch.int32)
+        n = lengths.to(device=device, dtype=torch.int64)
+        return torch.where((n >= 1) & (n <= T), n, torch.full_like(n, T)).to(torch.int32)
 
     def _forward_hip(self, x, lengths):
         """GPU form: the three input projections of all T steps as one batched GEMM, then ops.GruSequence (per step one
@@ -136,7 +153,8 @@ class BayesianGRU(nn.Module):
         w_in = ops.stack_params([m.weight for m in inp])
         b_in = ops.stack_params([m.bias for m in inp]) if inp[0].bias is not None else None
         gi = ops.batched_linear(xg, w_in, b_in, group_first=True).view(3, B, T, self.hidden_size)
-        out = ops.gru_sequence(gi, ops.stack_params([m.weight for m in hid]), mh, self.af, self.compute_dtype)      # [T,B,H]
+        out = ops.gru_sequence(gi, ops.stack_params([m.weight for m in hid]), mh, self.af, self.compute_dtype,
+                               lens=self._steps(lengths, B, T, x.device))                                            # [T,B,H]
         if not self.return_last:
             return out.transpose(0, 1)
         self.all_hiddens = out.detach().transpose(0, 1)
@@ -175,12 +193,14 @@ class BayesianGRU(nn.Module):
             gi = [ops.linear(x if m is None else x * m, lin.weight, lin.bias)                # (replay-safe bias gradient)
                   for lin, m in zip((c.weight_ir, c.weight_ii, c.weight_in), mx)]
         outs = []
+        steps = self._steps(lengths, B, T, x.device)                           # length-aware: a row past its end keeps its state
         for t in range(T):
             hr, hi, hn = (h if m is None else h * m for m in mh)
             r = torch.sigmoid(gi[0][:, t] + recurrent(c.weight_hr, hr))
             i = torch.sigmoid(gi[1][:, t] + recurrent(c.weight_hi, hi))
             n = af(gi[2][:, t] + r * recurrent(c.weight_hn, hn))
-            h = (1 - i) * n + i * h
+            h_new = (1 - i) * n + i * h
+            h = h_new if steps is None else torch.where((steps > t).unsqueeze(1), h_new, h)
             outs.append(h)
         output = torch.stack(outs, dim=1)                                      # [B,T,hidden]
         if not self.return_last:
@@ -212,18 +232,32 @@ def encoder_input_dtype_from(encoder_input_dtype):
     return torch.bfloat16 if env == "bf16" else torch.float32
 
 
+def encoder_length_aware_from(encoder_length_aware):
+    """Whether the encoder a model builds is length-aware: the caller's ``encoder_length_aware`` (a bool), or, when that is None,
+    the environment variable VQA_ENCODER_LENGTHS (``0``, the default, or ``1``), read here -- where the encoder is built."""
+    if encoder_length_aware is not None:
+        if not isinstance(encoder_length_aware, bool):
+            raise ValueError("encoder_length_aware must be None, True or False, got %r" % (encoder_length_aware,))
+        return encoder_length_aware
+    env = os.environ.get("VQA_ENCODER_LENGTHS", "0")
+    if env not in ("0", "1"):
+        raise ValueError("VQA_ENCODER_LENGTHS must be 0 or 1, got %r" % (env,))
+    return env == "1"
+
+
 class SkipThoughts(nn.Module):
     """putils/__init__.py:878-985: ``forward(q_idxes int64 [B,T], 0 = PAD) -> [B,2400]``."""
 
     def __init__(self, vocab_list, data_dir=None, gru="BayesianGRU", return_last=True, af="tanh", pretrained=None,
-                 compute_dtype=None, input_dtype=None):
+                 compute_dtype=None, input_dtype=None, length_aware=False):
         super().__init__()
         if gru != "BayesianGRU":
             raise ValueError("only the BayesianGRU encoder of config/CoR2.py:166 / config/ODA.py:183 is provided")
         self.vocab_list, self.data_dir, self.af = vocab_list, data_dir, af
         self.embedding = nn.Embedding(num_embeddings=len(vocab_list), embedding_dim=620, padding_idx=0)
         self.gru = BayesianGRU(input_size=620, hidden_size=2400, dropout=0.25, return_last=return_last, af=af,
-                               compute_dtype=compute_dtype, input_dtype=input_dtype)
+                               compute_dtype=compute_dtype, input_dtype=input_dtype, length_aware=length_aware)
+        self.length_aware = self.gru.length_aware
         self.compute_dtype = self.gru.compute_dtype
         self.input_dtype = self.gru.input_dtype
         if pretrained is not None:

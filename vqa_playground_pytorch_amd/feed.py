@@ -537,8 +537,20 @@ def qa_table(store, qa_items, num_ans, q_dtype=torch.long, require_answers=False
     return _QaTable(store, qa_items, num_ans, q_dtype, require_answers)
 
 
+def _sorted_by_question_length(ids, q, shards):
+    """ids [b] reordered by descending count of non-zero tokens of q[ids], stably, inside each of the `shards` contiguous b // shards
+    slices (what `shard` hands to a rank); rows behind the last whole slice, which no rank receives, are sorted among themselves."""
+    ids = np.asarray(ids)
+    n = (q[ids] != 0).sum(axis=1)
+    per = len(ids) // shards
+    bounds = [r * per for r in range(shards)] + [shards * per, len(ids)] if per else [0, len(ids)]
+    parts = [lo + np.argsort(-n[lo:hi], kind="stable") for lo, hi in zip(bounds[:-1], bounds[1:]) if hi > lo]
+    return ids[np.concatenate(parts)] if parts else ids
+
+
 def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, pin=True, region_dtype=torch.float32, ring=3,
-                  q_dtype=torch.long, prefetch=0, epochs=1, producers=1, answers="dense", packed=False):
+                  q_dtype=torch.long, prefetch=0, epochs=1, producers=1, answers="dense", packed=False, sort_questions=False,
+                  shards=1):
     """The reference's loader (datasets.py:893-977: `Inner.__getitem__` + DataLoader(batch_size, shuffle, pin_memory=True), no
     drop_last) over a FeatureStore: yields batch dicts {'v' [B,N,D], 'q_idxes' [B,T], 'q_id' [B], 'a' [B,num_ans]} of host tensors.
     qa_items: the reference's per-question records -- 'img_filename' (or 'v_idx'), 'q_idxes', 'q_id', 'a_10_idx' [(answer id,
@@ -560,8 +572,15 @@ def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, p
     packed=True (a store with counts, padded or ragged): instead of 'v' the batches carry 'v_packed', the ring slot's capacity
     tensor [batch_size*N, D] of which the first sum(v_len) rows are the samples' real rows back to back (the rest is whatever the
     slot held: nothing reads it) -- the padding is neither gathered nor, through DevicePrefetcher, copied to the device; the
-    models unpack it there (ops.unpack_regions).  The short last batch yields the leading B_last*N rows."""
+    models unpack it there (ops.unpack_regions).  The short last batch yields the leading B_last*N rows.
+    sort_questions=True (token-id questions): each batch's record ids are reordered by descending question length (its count of
+    non-zero tokens) BEFORE anything is gathered -- a stable sort, so every key of the batch follows, packed rows included -- for
+    the length-aware question encoder, whose products skip row tiles that hold no unfinished question (SkipThoughts(length_aware=
+    True)).  shards=P: the sort happens inside each of the P contiguous B/P slices that `shard` hands to a rank, so ranks keep equal
+    work.  Which records make up a batch does not change, and order inside a batch does not change the training sum."""
     sparse = _check_answers(answers)
+    if int(shards) < 1:
+        raise ValueError("store_batches: shards must be >= 1, got %r" % (shards,))
     if packed and store.counts is None:
         raise ValueError("store_batches(packed=True) needs a store with region counts (FeatureStore(counts=) or (offsets=, regions=))")
     if not packed and getattr(store, "ragged", False):
@@ -575,6 +594,8 @@ def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, p
         return o
     table = qa_items if isinstance(qa_items, _QaTable) else _QaTable(store, qa_items, num_ans, q_dtype)
     T = table.q.shape[1]
+    if sort_questions and table.q.dtype.kind not in "iu":
+        raise ValueError("store_batches(sort_questions=True) sorts by the count of non-zero token ids: it needs q_dtype=torch.long")
     has_a = table.kind is not None
     K = table.padded_pairs()[0].shape[1] if sparse and has_a else 0       # (built here, before any producer thread runs)
     mk = (lambda *s, dtype: torch.empty(*s, dtype=dtype).pin_memory()) if pin else (lambda *s, dtype: torch.empty(*s, dtype=dtype))
@@ -586,6 +607,8 @@ def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, p
         order, lo = job
         ids = order[lo:lo + batch_size]
         b = len(ids)
+        if sort_questions:
+            ids = _sorted_by_question_length(ids, table.q, int(shards))
         with slot_lock:
             while len(slots) <= k:
                 v_shape = (batch_size * store.sample_shape[0], store.sample_shape[1]) if packed else (batch_size, *store.sample_shape)

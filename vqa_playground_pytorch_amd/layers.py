@@ -512,19 +512,21 @@ class RegionQuestionModel(nn.Module):
 
     compute_dtype = torch.float32       # storage type of the region-side tensors (cor2.Model sets its own)
 
-    def _set_seq2vec(self, seq2vec, vocab_words, encoder_dtype, encoder_input_dtype):
+    def _set_seq2vec(self, seq2vec, vocab_words, encoder_dtype, encoder_input_dtype, encoder_length_aware=None):
         """The ``seq2vec`` slot: "skipthoughts" (the reference's encoder, config/CoR2.py:166, randomly initialised here),
         "vector" / None (sample['q_idxes'] holds the 2400-d question vector) or the caller's own module."""
         if seq2vec == "skipthoughts":
-            from .encoder import SkipThoughts, encoder_dtype_from, encoder_input_dtype_from
+            from .encoder import SkipThoughts, encoder_dtype_from, encoder_input_dtype_from, encoder_length_aware_from
             seq2vec = SkipThoughts(vocab_list=vocab_words, gru="BayesianGRU", return_last=True, af="relu",
                                    compute_dtype=encoder_dtype_from(encoder_dtype),
-                                   input_dtype=encoder_input_dtype_from(encoder_input_dtype))
-        elif encoder_dtype is not None or encoder_input_dtype is not None:
+                                   input_dtype=encoder_input_dtype_from(encoder_input_dtype),
+                                   length_aware=encoder_length_aware_from(encoder_length_aware))
+        elif encoder_dtype is not None or encoder_input_dtype is not None or encoder_length_aware is not None:
             given = seq2vec if seq2vec is None or isinstance(seq2vec, str) else type(seq2vec).__name__
             raise ValueError("%s configures the SkipThoughts encoder that seq2vec='skipthoughts' builds; "
                              "it cannot be given with seq2vec=%r"
-                             % ("encoder_dtype" if encoder_dtype is not None else "encoder_input_dtype", given))
+                             % ("encoder_dtype" if encoder_dtype is not None else
+                                "encoder_input_dtype" if encoder_input_dtype is not None else "encoder_length_aware", given))
         if seq2vec == "vector":
             seq2vec = None
         self.seq2vec = seq2vec if seq2vec is not None else QuestionVectorInput(2400)

@@ -15,7 +15,7 @@ from .layers import MutanFusion, MyATT, MyConv1d, MyLinear, RegionQuestionModel,
 
 class Model(RegionQuestionModel):
     def __init__(self, vocab_words=None, num_ans=None, seq2vec=None, regions=36, encoder_dtype=None, encoder_input_dtype=None,
-                 region_counts=False):
+                 region_counts=False, encoder_length_aware=None):
         super().__init__()
         self.vocab_words = vocab_words
         self.num_classes = num_ans
@@ -25,7 +25,7 @@ class Model(RegionQuestionModel):
         # samples with more than j regions only.  False: the key is refused, as before.
         self.region_counts = bool(region_counts)
 
-        self._set_seq2vec(seq2vec, vocab_words, encoder_dtype, encoder_input_dtype)
+        self._set_seq2vec(seq2vec, vocab_words, encoder_dtype, encoder_input_dtype, encoder_length_aware)
         self.compress_v = MyConv1d(2048, 310, 1, 1, p=0.5, af="relu")
         self.compress_q = MyLinear(2400, 310, p=0.5, af="relu")
         self.att = MyATT(fuse_dim=regions * 310, glimpses=4, inputs_dim=2048, att_dim=620, af="relu")

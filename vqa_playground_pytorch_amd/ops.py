@@ -1642,16 +1642,20 @@ def split_weights(w, transposed=False):
     return img
 
 
-def gemm_nt_split_batched(a, a_off, a_gs, lda, img, c, bias, w, transposed, G, M, N, K, c_gs=None, ldc=None):
+def gemm_nt_split_batched(a, a_off, a_gs, lda, img, c, bias, w, transposed, G, M, N, K, c_gs=None, ldc=None, lens=None, t=0):
     """c[g] [M,N] = a_g [M,K] W_g^T (+ bias[g]) on the split engine, G problems in one launch.  a: a tensor holding the operands,
     a_g starting `a_off + g * a_gs` elements in, rows of stride lda; img = split_weights(w, transposed); c [G,M,N] contiguous, or
-    any layout with problem stride c_gs and row stride ldc (elements)."""
+    any layout with problem stride c_gs and row stride ldc (elements).  lens (int32 [M], device) and t: vqa_gemm_nt_split_batched_len
+    -- row tiles without a row of lens > t are not computed and keep what c held."""
     L_ = _lib.lib()
     ptr = ctypes.c_void_p(a.data_ptr() + 4 * int(a_off))
     w_sn, w_sk = (1, w.stride(1)) if transposed else (w.stride(1), 1)
-    _launch("gemm_nt_split_batched", (G, M, N, K), L_.vqa_gemm_nt_split_batched, ptr, int(a_gs), int(lda), _p(img), _p(c),
+    name, fn, tail = "gemm_nt_split_batched", L_.vqa_gemm_nt_split_batched, ()
+    if lens is not None:
+        name, fn, tail = "gemm_nt_split_batched_len", L_.vqa_gemm_nt_split_batched_len, (_p(lens), int(t))
+    _launch(name, (G, M, N, K), fn, ptr, int(a_gs), int(lda), _p(img), _p(c),
             M * N if c_gs is None else int(c_gs), N if ldc is None else int(ldc),
-            _p(bias), bias.stride(0) if bias is not None else 0, _p(w), w.stride(0), int(w_sn), int(w_sk), G, M, N, K)
+            _p(bias), bias.stride(0) if bias is not None else 0, _p(w), w.stride(0), int(w_sn), int(w_sk), G, M, N, K, *tail)
     return c
 
 
@@ -1690,9 +1694,18 @@ def _grouped_products(name, problems, engine=None):
     ph.run()
 
 
-def _gru_forward(ctx, gi, w, masks, af, bf16):
+def _gru_lens(lens, B, device):
+    """the per-row step counts of the length-aware path: an int32 [B] tensor on the GPU, never read by the host"""
+    if not isinstance(lens, torch.Tensor) or lens.dtype != torch.int32 or tuple(lens.shape) != (B,) or lens.device != device:
+        raise ValueError("gru_sequence: lens must be an int32 [B] tensor on the device of gi (1 <= lens[b] <= T)")
+    return lens.contiguous()
+
+
+def _gru_forward(ctx, gi, w, masks, af, bf16, lens=None):
     """forward of GruSequence (bf16 False) and GruSequenceBf16 (True): one loop; the two differ in the history's dtype and row
-    length, in how W is prepared once per pass, in the step product and in the gate entry point (which takes the row length)."""
+    length, in how W is prepared once per pass, in the step product and in the gate entry point (which takes the row length).
+    lens (the *Len Functions): the `_len` entry points -- the gate kernels always, the products where they are the batched split
+    kernel or the bf16 kernel (the grouped fallback stays the full launch: correct, merely not faster)."""
     from . import head
     gi, w = _prep("gi", gi), _prep("w", w)
     masks = _prep("masks", masks) if masks is not None else None
@@ -1716,11 +1729,20 @@ def _gru_forward(ctx, gi, w, masks, af, bf16):
     else:
         fast = gemm_nt_split_batched_ok(B, H, H, H, hist, w)
         img = split_weights(w) if fast else None
+    if lens is not None:
+        lens = _gru_lens(lens, B, dev)
     name, fn = _entry("gru_gates_fwd", hist.dtype)
+    if lens is not None:
+        name, fn = name + "_len", getattr(_lib.lib(), "vqa_" + name + "_len")
     row = (Hp,) if bf16 else ()
+    cnt = (_p(lens),) if lens is not None else ()
     for t in range(T):
         if t == 0:
             a.zero_()                                                        # hm_0 = 0: no product to form
+        elif bf16 and lens is not None:
+            gru_gemm_bf16(hist, t * B * Hp, gs, Hp, wb, H * Hp, Hp, a, 3, B, H, H, lens=lens, t=t)
+        elif fast and lens is not None:
+            gemm_nt_split_batched(hist, t * B * H, gs, H, img, a, None, w, False, 3, B, H, H, lens=lens, t=t)
         elif bf16:
             gru_gemm_bf16(hist, t * B * Hp, gs, Hp, wb, H * Hp, Hp, a, 3, B, H, H)                      # a[g] = hm_t[g] Wb_g^T
         elif fast:
@@ -1729,8 +1751,11 @@ def _gru_forward(ctx, gi, w, masks, af, bf16):
             _grouped_products("gru_step_fwd", [(head.NT, hist, g * gs + t * B * H, H, w, g * H * H, H, B, H, H, a[g]) for g in range(3)])
         nxt = ctypes.c_void_p(hist.data_ptr() + hist.element_size() * (t + 1) * B * Hp) if t + 1 < T else None
         _launch(name, (B, T, H), fn, _p(gi), _p(a), _p(out[t - 1] if t else h0), _p(masks), _p(out[t]), nxt, gs, *row,
-                _p(saved[0, t]), _p(saved[1, t]), _p(saved[2, t]), _p(saved[3, t]), B, T, H, t, code)
-    ctx.save_for_backward(w, masks, out, hist, saved, h0)
+                _p(saved[0, t]), _p(saved[1, t]), _p(saved[2, t]), _p(saved[3, t]), *cnt, B, T, H, t, code)
+    if lens is not None:
+        ctx.save_for_backward(w, masks, out, hist, saved, h0, lens)
+    else:
+        ctx.save_for_backward(w, masks, out, hist, saved, h0)
     ctx.cfg = (B, T, H, Hp, code, fast)
     return out
 
@@ -1739,7 +1764,8 @@ def _gru_backward(ctx, d_out, bf16):
     """backward of both GRU Functions: the gate gradients step by step, the data-gradient product against W^T (prepared once),
     then the recurrent weight gradient over all T*B rows of the two histories."""
     from . import head
-    w, masks, out, hist, saved, h0 = ctx.saved_tensors
+    w, masks, out, hist, saved, h0, *lens = ctx.saved_tensors
+    lens = lens[0] if lens else None
     B, T, H, Hp, code, fast = ctx.cfg
     d_out = _prep("grad_out", d_out)
     dev = d_out.device
@@ -1757,15 +1783,23 @@ def _gru_backward(ctx, d_out, bf16):
     else:
         img_t = split_weights(w, transposed=True) if fast else None
     name, fn = _entry("gru_gates_bwd", hist.dtype)
+    if lens is not None:
+        name, fn = name + "_len", getattr(L_, "vqa_" + name + "_len")
     row = (Hp,) if bf16 else ()
+    cnt = (_p(lens),) if lens is not None else ()
     dhm = None
     for t in range(T - 1, -1, -1):
         _launch(name, (B, T, H), fn, _p(d_out[t]), _p(carry[(t + 1) & 1]) if t + 1 < T else None, _p(dhm), _p(masks),
                 _p(saved[0, t]), _p(saved[1, t]), _p(saved[2, t]), _p(saved[3, t]), _p(out[t - 1] if t else h0),
-                ctypes.c_void_p(gz.data_ptr() + gz.element_size() * t * B * Hp), gs, *row, _p(d_gi), _p(carry[t & 1]), B, T, H, t, code)
+                ctypes.c_void_p(gz.data_ptr() + gz.element_size() * t * B * Hp), gs, *row, _p(d_gi), _p(carry[t & 1]), *cnt, B, T, H, t,
+                code)
         if t == 0:
             break
-        if bf16:                                                            # gradient at hm_t: dhm[g] = gz_t[g] W_g   [3,B,H]
+        if bf16 and lens is not None:                                       # (its reader, gate step t - 1, reads dhm[b] iff t < lens[b])
+            dhm = gru_gemm_bf16(gz, t * B * Hp, gs, Hp, wbt, H * Hp, Hp, buf, 3, B, H, H, lens=lens, t=t)
+        elif fast and lens is not None:
+            dhm = gemm_nt_split_batched(gz, t * B * H, gs, H, img_t, buf, None, w, True, 3, B, H, H, lens=lens, t=t)
+        elif bf16:                                                            # gradient at hm_t: dhm[g] = gz_t[g] W_g   [3,B,H]
             dhm = gru_gemm_bf16(gz, t * B * Hp, gs, Hp, wbt, H * Hp, Hp, buf, 3, B, H, H)
         elif fast:
             dhm = gemm_nt_split_batched(gz, t * B * H, gs, H, img_t, buf, None, w, True, 3, B, H, H)
@@ -1786,7 +1820,7 @@ def _gru_backward(ctx, d_out, bf16):
             if rest:      # (short sequences / odd widths: the grouped launch, contraction split into slabs and summed in fixed order)
                 _grouped_products("gru_dw", [(head.TN, gz, g * gs, H, hist, g * gs, H, H, H, T * B, d_w[g]) for g in rest],
                                   engine="split" if (f32_products() == "split" and T * B >= 384) else None)
-    return d_gi, d_w, None, None
+    return (d_gi, d_w, None, None) if lens is None else (d_gi, d_w, None, None, None)
 
 
 class GruSequence(torch.autograd.Function):
@@ -1809,12 +1843,16 @@ class GruSequence(torch.autograd.Function):
         return _gru_backward(ctx, d_out, False)
 
 
-def gru_gemm_bf16(a, a_off, a_gs, lda, w, w_gs, ldw, c, G, M, N, K):
+def gru_gemm_bf16(a, a_off, a_gs, lda, w, w_gs, ldw, c, G, M, N, K, lens=None, t=0):
     """c[g] [M,N] fp32 (contiguous [G,M,N]) = a_g [M,K] w_g[N,K]^T, one bf16 product each with fp32 accumulation
     (csrc/gru_bf16.hip: vqa_gru_gemm_bf16).  a, w: bf16 tensors holding the operands, a_g starting `a_off + g * a_gs` elements in,
-    rows of stride lda / ldw whose pads up to a multiple of 64 elements are zero."""
-    _launch("gru_gemm_bf16", (G, M, N, K), _lib.lib().vqa_gru_gemm_bf16, ctypes.c_void_p(a.data_ptr() + 2 * int(a_off)), int(a_gs),
-            int(lda), _p(w), int(w_gs), int(ldw), _p(c), M * N, N, G, M, N, K)
+    rows of stride lda / ldw whose pads up to a multiple of 64 elements are zero.  lens (int32 [M], device) and t:
+    vqa_gru_gemm_bf16_len -- row tiles without a row of lens > t are not computed and keep what c held."""
+    name, fn, tail = "gru_gemm_bf16", _lib.lib().vqa_gru_gemm_bf16, ()
+    if lens is not None:
+        name, fn, tail = "gru_gemm_bf16_len", _lib.lib().vqa_gru_gemm_bf16_len, (_p(lens), int(t))
+    _launch(name, (G, M, N, K), fn, ctypes.c_void_p(a.data_ptr() + 2 * int(a_off)), int(a_gs),
+            int(lda), _p(w), int(w_gs), int(ldw), _p(c), M * N, N, G, M, N, K, *tail)
     return c
 
 
@@ -1847,12 +1885,43 @@ def parse_compute_dtype(value, name="compute_dtype"):
     raise ValueError("%s must be None, torch.float32 or torch.bfloat16, got %r" % (name, value))
 
 
-def gru_sequence(gi, w, masks, af, compute_dtype=None):
+class GruSequenceLen(torch.autograd.Function):
+    """GruSequence with per-row step counts lens [B] (int32, device, 1 <= lens[b] <= T; include/vqa_mi355x.h states the contract):
+    row b computes steps t < lens[b] exactly as GruSequence does and keeps its state afterwards, out[t,b] = out[lens[b]-1,b]; the
+    `_len` gate kernels (csrc/gru_len.hip) and, on the batched split path, the `_len` product, whose row tiles without an active
+    row return at once.  The weight-gradient launches are GruSequence's: they meet exact zeros at the inactive steps."""
+
+    @staticmethod
+    def forward(ctx, gi, w, masks, af, lens):
+        return _gru_forward(ctx, gi, w, masks, af, False, lens)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        return _gru_backward(ctx, d_out, False)
+
+
+class GruSequenceBf16Len(torch.autograd.Function):
+    """GruSequenceBf16 with per-row step counts: GruSequenceLen's rule on the mixed-precision kernels."""
+
+    @staticmethod
+    def forward(ctx, gi, w, masks, af, lens):
+        return _gru_forward(ctx, gi, w, masks, af, True, lens)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        return _gru_backward(ctx, d_out, True)
+
+
+def gru_sequence(gi, w, masks, af, compute_dtype=None, lens=None):
     """compute_dtype None / torch.float32: GruSequence (fp32 products on the split engine); torch.bfloat16 / 'bf16' / 'bfloat16':
-    GruSequenceBf16 (one bf16 product per recurrent GEMM, fp32 accumulation)."""
+    GruSequenceBf16 (one bf16 product per recurrent GEMM, fp32 accumulation).  lens (int32 [B] on the device, 1 <= lens[b] <= T;
+    None: the paths above, call for call): the length-aware twins GruSequenceLen / GruSequenceBf16Len."""
     if af not in ("relu", "tanh"):
         raise ValueError("gru_sequence: af must be 'relu' or 'tanh', got %r" % (af,))
-    if parse_compute_dtype(compute_dtype) == torch.bfloat16:
+    bf16 = parse_compute_dtype(compute_dtype) == torch.bfloat16
+    if lens is not None:
+        return (GruSequenceBf16Len if bf16 else GruSequenceLen).apply(gi, w, masks, af, lens)
+    if bf16:
         return GruSequenceBf16.apply(gi, w, masks, af)
     return GruSequence.apply(gi, w, masks, af)
 
