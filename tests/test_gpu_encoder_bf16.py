@@ -1,4 +1,4 @@
-"""The question encoder's mixed-precision recurrent path on the GPU (csrc/gru_bf16.hip, ops.GruSequenceBf16):
+"""The question encoder's mixed-precision recurrent path on the GPU (csrc/gru_bf16.hip, csrc/gru.hip, ops.GruSequence(bf16=True)):
 
   kernel level    vqa_gru_gemm_bf16 exact on small integers (any accumulation order is exact below 2^24) in both uses -- the
                   forward's shadow and the transposed shadow of the data gradient --, against float64 on random bf16 operands,
@@ -48,7 +48,7 @@ def gemm_operands(shape, ints):
 
 
 def run_gemm(ops, shape, a, w, transposed):
-    """vqa_gru_gemm_bf16 the way ops.GruSequenceBf16 calls it: `a` in a zero-padded bf16 history slot, the weights' bf16 shadow
+    """vqa_gru_gemm_bf16 the way ops.GruSequence calls it: `a` in a zero-padded bf16 history slot, the weights' bf16 shadow
     packed from fp32 masters by vqa_pack_bf16 -- [N,K] masters as they are (the forward), or [K,N] masters into the transposed
     shadow (the data gradient) -- and c inside a larger sentinel-filled buffer (ldc > N, rows past M) -> c [G,M,N]."""
     G, M, N, K = shape

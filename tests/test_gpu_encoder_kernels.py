@@ -885,8 +885,8 @@ def _launch_steps(first, product, gate, T):
     return [first, gate] + [product, gate] * (T - 1)
 
 
-# Recorded from ops.GruSequence / ops.GruSequenceBf16 as they stood before the two shared one loop body (forward then backward, relu,
-# masks given, d_w wanted); (compute_dtype, B, T, H) -> names handed to ops._launch.  fp32: B = 2 takes the grouped fallback (every
+# Recorded from the fp32 and the bf16 autograd Function as they stood before the two shared one loop body (today both are
+# ops.GruSequence); forward then backward, relu, masks given, d_w wanted; (compute_dtype, B, T, H) -> names handed to ops._launch.  fp32: B = 2 takes the grouped fallback (every
 # product one direct-output grouped launch), B = 64, H = 324 the batched kernel (the smallest such case of section 5; 324 is outside
 # of vqa_gemm_tn_split: d_w is a grouped launch on the split engine with its epilogue).  bf16 has one path; H = 328 is 324 rounded
 # up to the multiple of 8 it needs.

@@ -159,6 +159,13 @@ def _gate_case(B, H, seed):
     return c
 
 
+def _len_instance(log, log0):
+    """the `_len` entry (log) launched the LEN = true instantiation of the kernel whose LEN = false instantiation the plain entry
+    (log0) launched, on the same grid"""
+    plain = log0[0][0]
+    return plain.endswith(",false>)") and log[0][0] == plain[:-len(",false>)")] + ",true>)" and log[0][1] == log0[0][1]
+
+
 def _gates_fwd(ops, c, bf, t, af, a, lens):
     L = ops._lib.lib()
     B, H = c["h_prev"].shape
@@ -188,7 +195,8 @@ def test_gates_fwd_len_with_poisoned_inactive_rows(ops, B, H, bf, af):
         poisoned[:, ~active] = NAN
         h_new, hm, saved, log = _gates_fwd(ops, c, bf, t, af, poisoned, c["lens"])
         ref_h, ref_hm, ref_saved, log0 = _gates_fwd(ops, c, bf, t, af, c["a"], None)
-        assert "_len_kernel" in log[0][0] and log[0][1] == log0[0][1], (log, log0)
+        # the LEN instantiation against the plain one of the same kernel, with the same grid
+        assert _len_instance(log, log0), (log, log0)
         act = active.to(dev())
         for name, got, ref in (("h_new", h_new, ref_h), ("hm_next", hm[:, :, :H].transpose(0, 1), ref_hm[:, :, :H].transpose(0, 1)),
                                ("saved", saved.transpose(0, 1), ref_saved.transpose(0, 1))):
@@ -237,7 +245,8 @@ def test_gates_bwd_len_with_poisoned_inactive_rows(ops, B, H, bf, af):
         dhm0 = c["dhm"].clone()
         dhm0[:, ~active_next] = 0.0
         ref_gz, ref_gi, ref_co, log0 = _gates_bwd(ops, c, bf, t, af, dhm0, c["saved"], None)
-        assert "_len_kernel" in log[0][0] and log[0][1] == log0[0][1], (log, log0)
+        # the LEN instantiation against the plain one of the same kernel, with the same grid
+        assert _len_instance(log, log0), (log, log0)
         act = active.to(dev())
         for name, got, ref in (("gz", gz[:, :, :H].transpose(0, 1), ref_gz[:, :, :H].transpose(0, 1)),
                                ("d_gi", d_gi[:, :, t].transpose(0, 1), ref_gi[:, :, t].transpose(0, 1)), ("carry_out", carry_out, ref_co)):
@@ -250,6 +259,28 @@ def test_gates_bwd_len_with_poisoned_inactive_rows(ops, B, H, bf, af):
         assert _same_bits(carry_out[~act], want_co[~act]), "t=%d: carry_out of the inactive rows" % t
         other = [s for s in range(GT) if s != t]
         assert _untouched(d_gi[:, :, other]) and _untouched(gz[:, :, H:]), "t=%d: a store outside slot t / into the row pads" % t
+
+
+@pytest.mark.parametrize("af", [1, 3], ids=["relu", "tanh"])
+@pytest.mark.parametrize("bf", [False, True], ids=["f32", "bf16"])
+@pytest.mark.parametrize("H", [16, 168])
+@pytest.mark.parametrize("B", [5, 160])
+def test_gates_len_with_every_row_active_equal_the_plain_entries(ops, B, H, bf, af):
+    """the two instantiations of csrc/gru.hip's kernel pair share their arithmetic: with lens = T for every row, at every t, every
+    output buffer of a `_len` entry is the plain entry's bit for bit, on all rows (sentinels outside the written slots included)"""
+    c = _gate_case(B, H, 41 * B + H)
+    full = torch.full((B,), GT, dtype=torch.int32)
+    for t in range(GT):
+        got = _gates_fwd(ops, c, bf, t, af, c["a"], full)
+        ref = _gates_fwd(ops, c, bf, t, af, c["a"], None)
+        assert _len_instance(got[3], ref[3]), (got[3], ref[3])
+        for name, x, y in zip(("h_new", "hm_next", "saved"), got, ref):
+            assert _same_bits(x, y), "forward t=%d: %s" % (t, name)
+        got = _gates_bwd(ops, c, bf, t, af, c["dhm"], c["saved"], full)
+        ref = _gates_bwd(ops, c, bf, t, af, c["dhm"], c["saved"], None)
+        assert _len_instance(got[3], ref[3]), (got[3], ref[3])
+        for name, x, y in zip(("gz", "d_gi", "carry_out"), got, ref):
+            assert _same_bits(x, y), "backward t=%d: %s" % (t, name)
 
 
 # ---- 3. BayesianGRU ----------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
-// Mixed-precision recurrent path of the BayesianGRU question encoder: the per-step products of ops.GruSequenceBf16 as ONE bf16
-// product each (v_mfma_f32_32x32x16_bf16: bf16 operands, fp32 accumulation) instead of the split engine's six partial products
-// (csrc/gru_gemm.hip), and the gate kernels of csrc/gru.hip with bf16 GEMM-operand histories.
+// Mixed-precision recurrent path of the BayesianGRU question encoder: the per-step products of ops.GruSequence(bf16=True) as ONE
+// bf16 product each (v_mfma_f32_32x32x16_bf16: bf16 operands, fp32 accumulation) instead of the split engine's six partial
+// products (csrc/gru_gemm.hip).  The gate kernels are csrc/gru.hip's, instantiated for bf16 GEMM-operand histories.
 //
 // Arithmetic contract (bf(.) = round to nearest even to bf16; step t of putils.BayesianGRU.forward, putils/__init__.py:604-646,
 // 691-731):
@@ -83,103 +83,6 @@ __global__ __launch_bounds__(kBfThreads) void gru_gemm_bf16_kernel(GruBfArgs q) 
   }
 }
 
-// ---- gate kernels: csrc/gru.hip's, with the GEMM-operand histories in bf16 ------------------------------------------------
-__device__ __forceinline__ float sigmoidf(float z) { return 1.f / (1.f + expf(-z)); }
-__device__ __forceinline__ float gru_af(float z, int af) { return af == 1 ? fmaxf(z, 0.f) : tanhf(z); }
-__device__ __forceinline__ float gru_af_grad(float n, int af) { return af == 1 ? (n > 0.f ? 1.f : 0.f) : 1.f - n * n; }
-
-#define VQA_GRU_FOR4(EXPR)                 \
-  {                                        \
-    { constexpr int c = 0; EXPR; }         \
-    { constexpr int c = 1; EXPR; }         \
-    { constexpr int c = 2; EXPR; }         \
-    { constexpr int c = 3; EXPR; }         \
-  }
-__device__ __forceinline__ float& f4(float4& v, int c) { return reinterpret_cast<float*>(&v)[c]; }
-__device__ __forceinline__ float f4(const float4& v, int c) { return reinterpret_cast<const float*>(&v)[c]; }
-
-// as gru_gates_fwd_kernel; hm_next: base of slot t+1 of the bf16 [3,T,B,ld] history (group stride hist_gs, row stride ld) or null
-__global__ __launch_bounds__(256) void gru_gates_fwd_bf16_kernel(const float* __restrict__ gi, const float* __restrict__ a,
-                                                                 const float* __restrict__ h_prev,
-                                                                 const float* __restrict__ masks, float* __restrict__ h_new,
-                                                                 bf16* __restrict__ hm_next, size_t hist_gs, int ld,
-                                                                 float* __restrict__ r_s, float* __restrict__ i_s,
-                                                                 float* __restrict__ n_s, float* __restrict__ an_s, int B, int T,
-                                                                 int H, int t, int af) {
-  const size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
-  const size_t BH = (size_t)B * H;
-  if (e >= BH) return;
-  const size_t b = e / H, h = e % H;
-  const size_t gio = (b * T + t) * H + h, gig = (size_t)B * T * H;
-  const float4 gr = ld4(gi + gio), gz = ld4(gi + gig + gio), gn = ld4(gi + 2 * gig + gio);
-  const float4 ar = ld4(a + e), ai = ld4(a + BH + e), an = ld4(a + 2 * BH + e);
-  const float4 hp = ld4(h_prev + e);
-  float4 r, i, n, hn;
-  VQA_GRU_FOR4(f4(r, c) = sigmoidf(f4(gr, c) + f4(ar, c)); f4(i, c) = sigmoidf(f4(gz, c) + f4(ai, c));
-               f4(n, c) = gru_af(f4(gn, c) + f4(r, c) * f4(an, c), af);
-               f4(hn, c) = (1.f - f4(i, c)) * f4(n, c) + f4(i, c) * f4(hp, c));
-  st4(h_new + e, hn);
-  st4(r_s + e, r);
-  st4(i_s + e, i);
-  st4(n_s + e, n);
-  st4(an_s + e, an);
-  if (hm_next != nullptr) {
-    const size_t ho = b * (size_t)ld + h;
-#pragma unroll
-    for (int g = 0; g < 3; ++g) st4(hm_next + g * hist_gs + ho, masks != nullptr ? mul4(hn, ld4(masks + g * BH + e)) : hn);
-  }
-}
-
-// as gru_gates_bwd_kernel; gz: slot t of the bf16 [3,T,B,ld] history (bf(dzr), bf(dzi), bf(dan)); d_gi stays fp32, unrounded
-__global__ __launch_bounds__(256) void gru_gates_bwd_bf16_kernel(const float* __restrict__ d_out_t,
-                                                                 const float* __restrict__ carry_in,
-                                                                 const float* __restrict__ dhm, const float* __restrict__ masks,
-                                                                 const float* __restrict__ r_s, const float* __restrict__ i_s,
-                                                                 const float* __restrict__ n_s, const float* __restrict__ an_s,
-                                                                 const float* __restrict__ h_prev, bf16* __restrict__ gz,
-                                                                 size_t hist_gs, int ld, float* __restrict__ d_gi,
-                                                                 float* __restrict__ carry_out, int B, int T, int H, int t,
-                                                                 int af) {
-  const size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
-  const size_t BH = (size_t)B * H;
-  if (e >= BH) return;
-  const size_t b = e / H, h = e % H;
-  float4 dh = d_out_t != nullptr ? ld4(d_out_t + e) : make_float4(0.f, 0.f, 0.f, 0.f);
-  if (carry_in != nullptr) dh = add4(dh, ld4(carry_in + e));
-  if (dhm != nullptr) {
-#pragma unroll
-    for (int g = 0; g < 3; ++g) {
-      const float4 d = ld4(dhm + g * BH + e);
-      dh = add4(dh, masks != nullptr ? mul4(d, ld4(masks + g * BH + e)) : d);
-    }
-  }
-  const float4 r = ld4(r_s + e), i = ld4(i_s + e), n = ld4(n_s + e), an = ld4(an_s + e), hp = ld4(h_prev + e);
-  float4 dzr, dzi, dzn, dan, co;
-  VQA_GRU_FOR4(const float d = f4(dh, c); const float dn = d * (1.f - f4(i, c)) * gru_af_grad(f4(n, c), af);
-               f4(dzn, c) = dn; f4(dan, c) = dn * f4(r, c);
-               f4(dzr, c) = dn * f4(an, c) * f4(r, c) * (1.f - f4(r, c));
-               f4(dzi, c) = d * (f4(hp, c) - f4(n, c)) * f4(i, c) * (1.f - f4(i, c)); f4(co, c) = d * f4(i, c));
-  const size_t ho = b * (size_t)ld + h;
-  st4(gz + ho, dzr);
-  st4(gz + hist_gs + ho, dzi);
-  st4(gz + 2 * hist_gs + ho, dan);
-  const size_t gio = (b * T + t) * H + h, gig = (size_t)B * T * H;
-  st4(d_gi + gio, dzr);
-  st4(d_gi + gig + gio, dzi);
-  st4(d_gi + 2 * gig + gio, dzn);
-  st4(carry_out + e, co);
-}
-
-static int gru_bf16_check(const char* who, const void* hist, size_t hist_gs, int ld, int B, int T, int H, int t, int af) {
-  VQA_REQUIRE(B > 0 && T > 0 && H > 0 && t >= 0 && t < T, VQA_E_BADARG, "%s: bad sizes B=%d T=%d H=%d t=%d", who, B, T, H, t);
-  VQA_REQUIRE(H % 8 == 0, VQA_E_UNSUPPORTED, "%s: needs H %% 8 == 0 (H=%d)", who, H);
-  VQA_REQUIRE(af == 1 || af == 3, VQA_E_BADARG, "%s: af must be 1 (relu) or 3 (tanh), got %d", who, af);
-  VQA_REQUIRE(hist == nullptr || ld >= H, VQA_E_BADARG, "%s: history row stride %d < H=%d", who, ld, H);
-  VQA_REQUIRE(hist == nullptr || (ld % 8 == 0 && hist_gs % 8 == 0 && aligned(hist, 16)), VQA_E_UNSUPPORTED,
-              "%s: the bf16 history needs ld %% 8 == 0, a group stride %% 8 == 0 and a 16-byte aligned slot", who);
-  return VQA_OK;
-}
-
 template <int BM, int BN, bool LEN = false>
 static int launch_gru_gemm_bf16(GruBfArgs q, int G, hipStream_t s) {
   q.tiles_m = (q.M + BM - 1) / BM;
@@ -240,29 +143,3 @@ extern "C" int vqa_gru_gemm_bf16_len(const vqa_bf16_t* a, long a_gs, int lda, co
 }
 
 extern "C" int vqa_gru_gemm_bf16_tile_rows(int M) { return M <= 64 ? 64 : 128; }
-
-extern "C" int vqa_gru_gates_fwd_bf16(const float* gi, const float* a, const float* h_prev, const float* masks, float* h_new,
-                                      vqa_bf16_t* hm_next, size_t hist_group_stride, int ld, float* r_s, float* i_s, float* n_s,
-                                      float* an_s, int B, int T, int H, int t, int af, vqa_stream_t stream) {
-  VQA_REQUIRE(gi && a && h_prev && h_new && r_s && i_s && n_s && an_s, VQA_E_BADARG, "gru_gates_fwd_bf16: null pointer");
-  int rc = gru_bf16_check("gru_gates_fwd_bf16", hm_next, hist_group_stride, ld, B, T, H, t, af);
-  if (rc != VQA_OK) return rc;
-  const size_t n4 = (size_t)B * H / 4;
-  VQA_LAUNCH(gru_gates_fwd_bf16_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), gi,
-             a, h_prev, masks, h_new, reinterpret_cast<bf16*>(hm_next), hist_group_stride, ld, r_s, i_s, n_s, an_s, B, T, H, t, af);
-  return check_launch("gru_gates_fwd_bf16");
-}
-
-extern "C" int vqa_gru_gates_bwd_bf16(const float* d_out_t, const float* carry_in, const float* dhm, const float* masks,
-                                      const float* r_s, const float* i_s, const float* n_s, const float* an_s,
-                                      const float* h_prev, vqa_bf16_t* gz, size_t hist_group_stride, int ld, float* d_gi,
-                                      float* carry_out, int B, int T, int H, int t, int af, vqa_stream_t stream) {
-  VQA_REQUIRE(r_s && i_s && n_s && an_s && h_prev && gz && d_gi && carry_out, VQA_E_BADARG, "gru_gates_bwd_bf16: null pointer");
-  int rc = gru_bf16_check("gru_gates_bwd_bf16", gz, hist_group_stride, ld, B, T, H, t, af);
-  if (rc != VQA_OK) return rc;
-  const size_t n4 = (size_t)B * H / 4;
-  VQA_LAUNCH(gru_gates_bwd_bf16_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-             d_out_t, carry_in, dhm, masks, r_s, i_s, n_s, an_s, h_prev, reinterpret_cast<bf16*>(gz), hist_group_stride, ld, d_gi,
-             carry_out, B, T, H, t, af);
-  return check_launch("gru_gates_bwd_bf16");
-}

@@ -139,7 +139,8 @@ class BayesianGRU(nn.Module):
 
     def _forward_hip(self, x, lengths):
         """GPU form: the three input projections of all T steps as one batched GEMM, then ops.GruSequence (per step one
-        batched recurrent GEMM + one gate kernel; csrc/gru.hip)."""
+        batched recurrent GEMM + one gate kernel, csrc/gru.hip; compute_dtype and the step counts pick its products and entry
+        points)."""
         c = self.gru_cell
         B, T, K = x.shape
         inp, hid = (c.weight_ir, c.weight_ii, c.weight_in), (c.weight_hr, c.weight_hi, c.weight_hn)

@@ -1701,148 +1701,6 @@ def _gru_lens(lens, B, device):
     return lens.contiguous()
 
 
-def _gru_forward(ctx, gi, w, masks, af, bf16, lens=None):
-    """forward of GruSequence (bf16 False) and GruSequenceBf16 (True): one loop; the two differ in the history's dtype and row
-    length, in how W is prepared once per pass, in the step product and in the gate entry point (which takes the row length).
-    lens (the *Len Functions): the `_len` entry points -- the gate kernels always, the products where they are the batched split
-    kernel or the bf16 kernel (the grouped fallback stays the full launch: correct, merely not faster)."""
-    from . import head
-    gi, w = _prep("gi", gi), _prep("w", w)
-    masks = _prep("masks", masks) if masks is not None else None
-    G, B, T, H = gi.shape
-    if G != 3 or w.shape != (3, H, H) or (masks is not None and masks.shape != (3, B, H)):
-        raise ValueError("gru_sequence: gi [3,B,T,H], w [3,H,H], masks [3,B,H] expected")
-    if bf16 and H % 8:
-        raise ValueError("gru_sequence: compute_dtype=bfloat16 needs a hidden size that is a multiple of 8, got H = %d" % H)
-    code = {"relu": 1, "tanh": 3}[af]
-    dev = gi.device
-    Hp = pad_to(H) if bf16 else H                                          # bf16: rows padded to a multiple of 64, pads never written
-    out = torch.empty(T, B, H, device=dev, dtype=torch.float32)
-    hist = torch.zeros(3, T, B, Hp, device=dev, dtype=torch.bfloat16 if bf16 else torch.float32)   # hm_t = h_{t-1} * m_g; hm_0 = 0
-    saved = torch.empty(4, T, B, H, device=dev, dtype=torch.float32)       # r, i, n, a_n
-    h0 = torch.zeros(B, H, device=dev, dtype=torch.float32)
-    a = torch.empty(3, B, H, device=dev, dtype=torch.float32)
-    gs = T * B * Hp
-    fast = None
-    if bf16:
-        wb = pack_bf16(w, torch.zeros(3, H, Hp, device=dev, dtype=torch.bfloat16), H * Hp, Hp, 1, zero_fill=False)
-    else:
-        fast = gemm_nt_split_batched_ok(B, H, H, H, hist, w)
-        img = split_weights(w) if fast else None
-    if lens is not None:
-        lens = _gru_lens(lens, B, dev)
-    name, fn = _entry("gru_gates_fwd", hist.dtype)
-    if lens is not None:
-        name, fn = name + "_len", getattr(_lib.lib(), "vqa_" + name + "_len")
-    row = (Hp,) if bf16 else ()
-    cnt = (_p(lens),) if lens is not None else ()
-    for t in range(T):
-        if t == 0:
-            a.zero_()                                                        # hm_0 = 0: no product to form
-        elif bf16 and lens is not None:
-            gru_gemm_bf16(hist, t * B * Hp, gs, Hp, wb, H * Hp, Hp, a, 3, B, H, H, lens=lens, t=t)
-        elif fast and lens is not None:
-            gemm_nt_split_batched(hist, t * B * H, gs, H, img, a, None, w, False, 3, B, H, H, lens=lens, t=t)
-        elif bf16:
-            gru_gemm_bf16(hist, t * B * Hp, gs, Hp, wb, H * Hp, Hp, a, 3, B, H, H)                      # a[g] = hm_t[g] Wb_g^T
-        elif fast:
-            gemm_nt_split_batched(hist, t * B * H, gs, H, img, a, None, w, False, 3, B, H, H)          # a[g] = hm_t[g] W_g^T
-        else:
-            _grouped_products("gru_step_fwd", [(head.NT, hist, g * gs + t * B * H, H, w, g * H * H, H, B, H, H, a[g]) for g in range(3)])
-        nxt = ctypes.c_void_p(hist.data_ptr() + hist.element_size() * (t + 1) * B * Hp) if t + 1 < T else None
-        _launch(name, (B, T, H), fn, _p(gi), _p(a), _p(out[t - 1] if t else h0), _p(masks), _p(out[t]), nxt, gs, *row,
-                _p(saved[0, t]), _p(saved[1, t]), _p(saved[2, t]), _p(saved[3, t]), *cnt, B, T, H, t, code)
-    if lens is not None:
-        ctx.save_for_backward(w, masks, out, hist, saved, h0, lens)
-    else:
-        ctx.save_for_backward(w, masks, out, hist, saved, h0)
-    ctx.cfg = (B, T, H, Hp, code, fast)
-    return out
-
-
-def _gru_backward(ctx, d_out, bf16):
-    """backward of both GRU Functions: the gate gradients step by step, the data-gradient product against W^T (prepared once),
-    then the recurrent weight gradient over all T*B rows of the two histories."""
-    from . import head
-    w, masks, out, hist, saved, h0, *lens = ctx.saved_tensors
-    lens = lens[0] if lens else None
-    B, T, H, Hp, code, fast = ctx.cfg
-    d_out = _prep("grad_out", d_out)
-    dev = d_out.device
-    L_ = _lib.lib()
-    if bf16:
-        gz = torch.zeros(3, T, B, Hp, device=dev, dtype=torch.bfloat16)        # gzb_t = bf(gz_t)
-    else:
-        gz = torch.empty(3, T, B, H, device=dev, dtype=torch.float32)
-    d_gi = torch.empty(3, B, T, H, device=dev, dtype=torch.float32)
-    carry = [torch.empty(B, H, device=dev, dtype=torch.float32) for _ in range(2)]
-    gs = T * B * Hp
-    buf = torch.empty(3, B, H, device=dev, dtype=torch.float32)
-    if bf16:
-        wbt = pack_bf16(w, torch.zeros(3, H, Hp, device=dev, dtype=torch.bfloat16), H * Hp, 1, Hp, zero_fill=False)   # Wb_g^T
-    else:
-        img_t = split_weights(w, transposed=True) if fast else None
-    name, fn = _entry("gru_gates_bwd", hist.dtype)
-    if lens is not None:
-        name, fn = name + "_len", getattr(L_, "vqa_" + name + "_len")
-    row = (Hp,) if bf16 else ()
-    cnt = (_p(lens),) if lens is not None else ()
-    dhm = None
-    for t in range(T - 1, -1, -1):
-        _launch(name, (B, T, H), fn, _p(d_out[t]), _p(carry[(t + 1) & 1]) if t + 1 < T else None, _p(dhm), _p(masks),
-                _p(saved[0, t]), _p(saved[1, t]), _p(saved[2, t]), _p(saved[3, t]), _p(out[t - 1] if t else h0),
-                ctypes.c_void_p(gz.data_ptr() + gz.element_size() * t * B * Hp), gs, *row, _p(d_gi), _p(carry[t & 1]), *cnt, B, T, H, t,
-                code)
-        if t == 0:
-            break
-        if bf16 and lens is not None:                                       # (its reader, gate step t - 1, reads dhm[b] iff t < lens[b])
-            dhm = gru_gemm_bf16(gz, t * B * Hp, gs, Hp, wbt, H * Hp, Hp, buf, 3, B, H, H, lens=lens, t=t)
-        elif fast and lens is not None:
-            dhm = gemm_nt_split_batched(gz, t * B * H, gs, H, img_t, buf, None, w, True, 3, B, H, H, lens=lens, t=t)
-        elif bf16:                                                            # gradient at hm_t: dhm[g] = gz_t[g] W_g   [3,B,H]
-            dhm = gru_gemm_bf16(gz, t * B * Hp, gs, Hp, wbt, H * Hp, Hp, buf, 3, B, H, H)
-        elif fast:
-            dhm = gemm_nt_split_batched(gz, t * B * H, gs, H, img_t, buf, None, w, True, 3, B, H, H)
-        else:
-            _grouped_products("gru_step_bwd", [(head.NN, gz, g * gs + t * B * H, H, w, g * H * H, H, B, H, H, buf[g]) for g in range(3)])
-            dhm = buf
-    d_w = None
-    if ctx.needs_input_grad[1]:
-        # d_w[g] = gz[g]^T hm[g] over all T*B rows, written straight into the gradient's slot
-        d_w = _grad_like(w)
-        if bf16:
-            ws, ws_bytes = _workspace(L_.vqa_gemm_bf16_tn_workspace_bytes, T * B, H, H, device=dev)
-            for g in range(3):
-                _launch("gemm_bf16_tn", (T * B, H, H), L_.vqa_gemm_bf16_tn, ctypes.c_void_p(gz.data_ptr() + 2 * g * gs), Hp,
-                        ctypes.c_void_p(hist.data_ptr() + 2 * g * gs), Hp, _p(d_w[g]), _p(ws), ws_bytes, T * B, H, H)
-        else:
-            rest = [g for g in range(3) if not (fast and gemm_tn_split(gz, g * gs, H, hist, g * gs, H, d_w[g], T * B, H, H))]
-            if rest:      # (short sequences / odd widths: the grouped launch, contraction split into slabs and summed in fixed order)
-                _grouped_products("gru_dw", [(head.TN, gz, g * gs, H, hist, g * gs, H, H, H, T * B, d_w[g]) for g in rest],
-                                  engine="split" if (f32_products() == "split" and T * B >= 384) else None)
-    return (d_gi, d_w, None, None) if lens is None else (d_gi, d_w, None, None, None)
-
-
-class GruSequence(torch.autograd.Function):
-    """The recurrent part of putils.BayesianGRU.forward (putils/__init__.py:704-731): T steps of
-    r,i = sigmoid(gi_{r,i}[t] + W_h{r,i}(h*m)), n = af(gi_n[t] + r * W_hn(h*m_n)), h = (1-i) n + i h.
-    gi [3,B,T,H] (the input-side projections of all steps), w [3,H,H] (W_hr, W_hi, W_hn stacked), masks [3,B,H] or
-    None (sequence-shared dropout) -> all hidden states [T,B,H].
-    Round 6: every product is the repo's own kernel (rounds 1-5: torch.bmm).  Per step ONE launch of the split engine's batched
-    NT GEMM (csrc/gru_gemm.hip: the three gates' [B,H] x [H,H]^T against weight images split once per pass -- W for the forward,
-    W^T for the data gradients) + ONE gate kernel (csrc/gru.hip) each way; the recurrent weight gradient is one grouped launch on
-    the split engine over all T*B rows at the end (csrc/grouped_gemm_split.hip, TN form).  Shapes the batched kernel does not take
-    (B < 64, H % 4) run the same products as grouped launches of the K6 engine."""
-
-    @staticmethod
-    def forward(ctx, gi, w, masks, af):
-        return _gru_forward(ctx, gi, w, masks, af, False)
-
-    @staticmethod
-    def backward(ctx, d_out):
-        return _gru_backward(ctx, d_out, False)
-
-
 def gru_gemm_bf16(a, a_off, a_gs, lda, w, w_gs, ldw, c, G, M, N, K, lens=None, t=0):
     """c[g] [M,N] fp32 (contiguous [G,M,N]) = a_g [M,K] w_g[N,K]^T, one bf16 product each with fp32 accumulation
     (csrc/gru_bf16.hip: vqa_gru_gemm_bf16).  a, w: bf16 tensors holding the operands, a_g starting `a_off + g * a_gs` elements in,
@@ -1856,21 +1714,137 @@ def gru_gemm_bf16(a, a_off, a_gs, lda, w, w_gs, ldw, c, G, M, N, K, lens=None, t
     return c
 
 
-class GruSequenceBf16(torch.autograd.Function):
-    """GruSequence with the recurrent products in mixed precision (csrc/gru_bf16.hip states the contract): bf16 shadows of the
-    three recurrent weights (packed once per forward pass, transposed once per backward pass; the masters stay fp32), bf16
-    histories of the GEMM operands hm_t = bf(h_{t-1} * m_g) and gzb_t = bf(gz_t) with rows padded to a multiple of 64 (zero pads,
-    never written), fp32 accumulation, fp32 state / gates / saved tensors / d_gi.  Per step one vqa_gru_gemm_bf16 and one
-    vqa_gru_gates_*_bf16 launch each way; the recurrent weight gradient is three vqa_gemm_bf16_tn launches (fixed-order slabs)
-    over the two histories at the end.  Any B >= 1, H % 8 == 0."""
+class GruSequence(torch.autograd.Function):
+    """The recurrent part of putils.BayesianGRU.forward (putils/__init__.py:704-731): T steps of
+    r,i = sigmoid(gi_{r,i}[t] + W_h{r,i}(h*m)), n = af(gi_n[t] + r * W_hn(h*m_n)), h = (1-i) n + i h.
+    gi [3,B,T,H] (the input-side projections of all steps), w [3,H,H] (W_hr, W_hi, W_hn stacked), masks [3,B,H] or
+    None (sequence-shared dropout) -> all hidden states [T,B,H].
+    Per step ONE product launch a[g] = hm_t[g] W_g^T (W^T's for the data gradients) against weights prepared once per pass + ONE
+    gate kernel (csrc/gru.hip) each way; the recurrent weight gradient runs over all T*B rows of the two histories at the end.
+    bf16 False: every product in fp32 on the split engine (csrc/gru_gemm.hip: the batched NT GEMM against weight images, the TN
+      weight-gradient kernels).  Shapes the batched kernel does not take (B < 64, H % 4) run the same products as grouped launches
+      of the K6 engine.
+    bf16 True: the products in mixed precision (csrc/gru_bf16.hip states the contract): bf16 shadows of the three recurrent
+      weights (the masters stay fp32), bf16 histories of the GEMM operands hm_t = bf(h_{t-1} * m_g) and gzb_t = bf(gz_t) with
+      rows padded to a multiple of 64 (zero pads, never written), fp32 accumulation, fp32 state / gates / saved tensors / d_gi;
+      vqa_gru_gemm_bf16 per step, three vqa_gemm_bf16_tn launches (fixed-order slabs) for the weight gradient.  Any B >= 1,
+      H % 8 == 0.
+    lens [B] (int32, device, 1 <= lens[b] <= T; include/vqa_mi355x.h states the contract) or None: row b computes steps
+      t < lens[b] exactly as without lens and keeps its state afterwards, out[t,b] = out[lens[b]-1,b] -- the `_len` entry points:
+      the gate kernels always, the products where they are the batched split kernel or the bf16 kernel, whose row tiles without an
+      active row return at once (the grouped fallback stays the full launch: correct, merely not faster).  The weight-gradient
+      launches are the same: they meet exact zeros at the inactive steps."""
 
     @staticmethod
-    def forward(ctx, gi, w, masks, af):
-        return _gru_forward(ctx, gi, w, masks, af, True)
+    def _step_product(cfg, src, t, wp, w, transposed, c, lens):
+        """c[g] [B,H] = src_t[g] W_g^T, or src_t[g] W_g when `transposed`; src: a [3,T,B,Hp] history, wp: W as prepared for the pass"""
+        from . import head
+        B, T, H, Hp, _, fast, bf16 = cfg
+        gs = T * B * Hp
+        if bf16:
+            return gru_gemm_bf16(src, t * B * Hp, gs, Hp, wp, H * Hp, Hp, c, 3, B, H, H, lens=lens, t=t)
+        if fast:
+            return gemm_nt_split_batched(src, t * B * H, gs, H, wp, c, None, w, transposed, 3, B, H, H, lens=lens, t=t)
+        _grouped_products("gru_step_bwd" if transposed else "gru_step_fwd",
+                          [(head.NN if transposed else head.NT, src, g * gs + t * B * H, H, w, g * H * H, H, B, H, H, c[g]) for g in range(3)])
+        return c
+
+    @staticmethod
+    def forward(ctx, gi, w, masks, af, bf16=False, lens=None):
+        gi, w = _prep("gi", gi), _prep("w", w)
+        masks = _prep("masks", masks) if masks is not None else None
+        G, B, T, H = gi.shape
+        if G != 3 or w.shape != (3, H, H) or (masks is not None and masks.shape != (3, B, H)):
+            raise ValueError("gru_sequence: gi [3,B,T,H], w [3,H,H], masks [3,B,H] expected")
+        if bf16 and H % 8:
+            raise ValueError("gru_sequence: compute_dtype=bfloat16 needs a hidden size that is a multiple of 8, got H = %d" % H)
+        code = {"relu": 1, "tanh": 3}[af]
+        dev = gi.device
+        Hp = pad_to(H) if bf16 else H                                          # bf16: rows padded to a multiple of 64, pads never written
+        out = torch.empty(T, B, H, device=dev, dtype=torch.float32)
+        hist = torch.zeros(3, T, B, Hp, device=dev, dtype=torch.bfloat16 if bf16 else torch.float32)   # hm_t = h_{t-1} * m_g; hm_0 = 0
+        saved = torch.empty(4, T, B, H, device=dev, dtype=torch.float32)       # r, i, n, a_n
+        h0 = torch.zeros(B, H, device=dev, dtype=torch.float32)
+        a = torch.empty(3, B, H, device=dev, dtype=torch.float32)
+        gs = T * B * Hp
+        fast = None
+        if bf16:
+            wp = pack_bf16(w, torch.zeros(3, H, Hp, device=dev, dtype=torch.bfloat16), H * Hp, Hp, 1, zero_fill=False)   # Wb_g
+        else:
+            fast = gemm_nt_split_batched_ok(B, H, H, H, hist, w)
+            wp = split_weights(w) if fast else None
+        if lens is not None:
+            lens = _gru_lens(lens, B, dev)
+        cfg = (B, T, H, Hp, code, fast, bool(bf16))
+        name, fn = _entry("gru_gates_fwd", hist.dtype)
+        if lens is not None:
+            name, fn = name + "_len", getattr(_lib.lib(), "vqa_" + name + "_len")
+        row = (Hp,) if bf16 else ()
+        cnt = (_p(lens),) if lens is not None else ()
+        for t in range(T):
+            if t == 0:
+                a.zero_()                                                        # hm_0 = 0: no product to form
+            else:
+                GruSequence._step_product(cfg, hist, t, wp, w, False, a, lens)   # a[g] = hm_t[g] W_g^T
+            nxt = ctypes.c_void_p(hist.data_ptr() + hist.element_size() * (t + 1) * B * Hp) if t + 1 < T else None
+            _launch(name, (B, T, H), fn, _p(gi), _p(a), _p(out[t - 1] if t else h0), _p(masks), _p(out[t]), nxt, gs, *row,
+                    _p(saved[0, t]), _p(saved[1, t]), _p(saved[2, t]), _p(saved[3, t]), *cnt, B, T, H, t, code)
+        ctx.save_for_backward(w, masks, out, hist, saved, h0, lens)
+        ctx.cfg = cfg
+        return out
 
     @staticmethod
     def backward(ctx, d_out):
-        return _gru_backward(ctx, d_out, True)
+        """the gate gradients step by step, the data-gradient product against W^T (prepared once), then the recurrent weight
+        gradient over all T*B rows of the two histories"""
+        from . import head
+        w, masks, out, hist, saved, h0, lens = ctx.saved_tensors
+        B, T, H, Hp, code, fast, bf16 = ctx.cfg
+        d_out = _prep("grad_out", d_out)
+        dev = d_out.device
+        L_ = _lib.lib()
+        if bf16:
+            gz = torch.zeros(3, T, B, Hp, device=dev, dtype=torch.bfloat16)        # gzb_t = bf(gz_t)
+        else:
+            gz = torch.empty(3, T, B, H, device=dev, dtype=torch.float32)
+        d_gi = torch.empty(3, B, T, H, device=dev, dtype=torch.float32)
+        carry = [torch.empty(B, H, device=dev, dtype=torch.float32) for _ in range(2)]
+        gs = T * B * Hp
+        buf = torch.empty(3, B, H, device=dev, dtype=torch.float32)
+        if bf16:
+            wpt = pack_bf16(w, torch.zeros(3, H, Hp, device=dev, dtype=torch.bfloat16), H * Hp, 1, Hp, zero_fill=False)   # Wb_g^T
+        else:
+            wpt = split_weights(w, transposed=True) if fast else None
+        name, fn = _entry("gru_gates_bwd", hist.dtype)
+        if lens is not None:
+            name, fn = name + "_len", getattr(L_, "vqa_" + name + "_len")
+        row = (Hp,) if bf16 else ()
+        cnt = (_p(lens),) if lens is not None else ()
+        dhm = None
+        for t in range(T - 1, -1, -1):
+            _launch(name, (B, T, H), fn, _p(d_out[t]), _p(carry[(t + 1) & 1]) if t + 1 < T else None, _p(dhm), _p(masks),
+                    _p(saved[0, t]), _p(saved[1, t]), _p(saved[2, t]), _p(saved[3, t]), _p(out[t - 1] if t else h0),
+                    ctypes.c_void_p(gz.data_ptr() + gz.element_size() * t * B * Hp), gs, *row, _p(d_gi), _p(carry[t & 1]), *cnt, B, T, H, t,
+                    code)
+            if t == 0:
+                break
+            # gradient at hm_t: dhm[g] = gz_t[g] W_g   [3,B,H]   (with lens its reader, gate step t - 1, reads dhm[b] iff t < lens[b])
+            dhm = GruSequence._step_product(ctx.cfg, gz, t, wpt, w, True, buf, lens)
+        d_w = None
+        if ctx.needs_input_grad[1]:
+            # d_w[g] = gz[g]^T hm[g] over all T*B rows, written straight into the gradient's slot
+            d_w = _grad_like(w)
+            if bf16:
+                ws, ws_bytes = _workspace(L_.vqa_gemm_bf16_tn_workspace_bytes, T * B, H, H, device=dev)
+                for g in range(3):
+                    _launch("gemm_bf16_tn", (T * B, H, H), L_.vqa_gemm_bf16_tn, ctypes.c_void_p(gz.data_ptr() + 2 * g * gs), Hp,
+                            ctypes.c_void_p(hist.data_ptr() + 2 * g * gs), Hp, _p(d_w[g]), _p(ws), ws_bytes, T * B, H, H)
+            else:
+                rest = [g for g in range(3) if not (fast and gemm_tn_split(gz, g * gs, H, hist, g * gs, H, d_w[g], T * B, H, H))]
+                if rest:      # (short sequences / odd widths: the grouped launch, contraction split into slabs and summed in fixed order)
+                    _grouped_products("gru_dw", [(head.TN, gz, g * gs, H, hist, g * gs, H, H, H, T * B, d_w[g]) for g in rest],
+                                      engine="split" if (f32_products() == "split" and T * B >= 384) else None)
+        return d_gi, d_w, None, None, None, None
 
 
 def parse_compute_dtype(value, name="compute_dtype"):
@@ -1885,45 +1859,13 @@ def parse_compute_dtype(value, name="compute_dtype"):
     raise ValueError("%s must be None, torch.float32 or torch.bfloat16, got %r" % (name, value))
 
 
-class GruSequenceLen(torch.autograd.Function):
-    """GruSequence with per-row step counts lens [B] (int32, device, 1 <= lens[b] <= T; include/vqa_mi355x.h states the contract):
-    row b computes steps t < lens[b] exactly as GruSequence does and keeps its state afterwards, out[t,b] = out[lens[b]-1,b]; the
-    `_len` gate kernels (csrc/gru_len.hip) and, on the batched split path, the `_len` product, whose row tiles without an active
-    row return at once.  The weight-gradient launches are GruSequence's: they meet exact zeros at the inactive steps."""
-
-    @staticmethod
-    def forward(ctx, gi, w, masks, af, lens):
-        return _gru_forward(ctx, gi, w, masks, af, False, lens)
-
-    @staticmethod
-    def backward(ctx, d_out):
-        return _gru_backward(ctx, d_out, False)
-
-
-class GruSequenceBf16Len(torch.autograd.Function):
-    """GruSequenceBf16 with per-row step counts: GruSequenceLen's rule on the mixed-precision kernels."""
-
-    @staticmethod
-    def forward(ctx, gi, w, masks, af, lens):
-        return _gru_forward(ctx, gi, w, masks, af, True, lens)
-
-    @staticmethod
-    def backward(ctx, d_out):
-        return _gru_backward(ctx, d_out, True)
-
-
 def gru_sequence(gi, w, masks, af, compute_dtype=None, lens=None):
-    """compute_dtype None / torch.float32: GruSequence (fp32 products on the split engine); torch.bfloat16 / 'bf16' / 'bfloat16':
-    GruSequenceBf16 (one bf16 product per recurrent GEMM, fp32 accumulation).  lens (int32 [B] on the device, 1 <= lens[b] <= T;
-    None: the paths above, call for call): the length-aware twins GruSequenceLen / GruSequenceBf16Len."""
+    """GruSequence.  compute_dtype None / torch.float32: fp32 products on the split engine; torch.bfloat16 / 'bf16' / 'bfloat16':
+    one bf16 product per recurrent GEMM, fp32 accumulation.  lens (int32 [B] on the device, 1 <= lens[b] <= T; None: the paths
+    above, call for call): the length-aware entry points."""
     if af not in ("relu", "tanh"):
         raise ValueError("gru_sequence: af must be 'relu' or 'tanh', got %r" % (af,))
-    bf16 = parse_compute_dtype(compute_dtype) == torch.bfloat16
-    if lens is not None:
-        return (GruSequenceBf16Len if bf16 else GruSequenceLen).apply(gi, w, masks, af, lens)
-    if bf16:
-        return GruSequenceBf16.apply(gi, w, masks, af)
-    return GruSequence.apply(gi, w, masks, af)
+    return GruSequence.apply(gi, w, masks, af, parse_compute_dtype(compute_dtype) == torch.bfloat16, lens)
 
 
 def _pack_stack_bf16(w, dst, batch_stride, row_stride, col_stride):
