@@ -15,7 +15,18 @@ sample N rows: packed cannot win, same bytes plus a pass) and `uniform` (10..N).
   step_ms      the captured step on resident inputs, 'v_packed' + 'v_len' against 'v' + 'v_len'
 Forms alternate in blocks inside one process; a figure is the median of its blocks, and the blocks are in the record.
 --parent-tree DIR: a checkout of the parent commit with its library built; its padded 'v' + 'v_len' step is then timed too, in
-child processes that alternate with this tree's."""
+child processes that alternate with this tree's.
+
+    python tools/feed_bench.py --resident [--store N_IMG] [--blocks 4] [--steps 30] [--iters 50]
+
+--resident: the device-resident region store (feed.DeviceFeatureStore) against the host feeds, as ONE JSON line on stdout, from one
+process in alternating blocks.  The store is the synthetic one of --store N_IMG (default 4096 images x 36 x 2048).
+  upload       seconds and nbytes of DeviceFeatureStore(store), fp32 and bf16
+  gather_us    vqa_gather_regions in its three forms beside vqa_unpack_regions at the same (B, N, D), B 512 x N 36 and
+               B 128 x N 100, microseconds per launch (every sample N rows: the same bytes move)
+  fed          samples/s of the captured B 512 x N 36 fp32 step: fed by store_batches(resident=) ('v_idx' batches, fp32 and bf16
+               store), fed from the memory-mapped host store with fp32 and bf16 transport, and on rotating batches that are
+               already on the device (no feed at all)"""
 import argparse
 import json
 import os
@@ -197,6 +208,106 @@ def _step_ms(cfg, kinds, args, dev, packed_forms):
     return rec
 
 
+def _unpack_vs_gather_us(B, N, n_img, args, dev):
+    """vqa_gather_regions against vqa_unpack_regions, every sample N rows, the three dtype forms; the store holds n_img images"""
+    from types import SimpleNamespace
+    from vqa_playground_pytorch_amd import ops
+    gen = torch.Generator().manual_seed(3)
+    idx = torch.randint(n_img, (B,), generator=gen).to(torch.int32).to(dev)
+    lens = torch.full((B,), N, dtype=torch.int32, device=dev)
+    starts = (torch.arange(n_img, dtype=torch.int64) * N).to(dev)
+    forms = {}
+    for name, dt_in, dt_out in (("f32", torch.float32, torch.float32), ("bf16", torch.bfloat16, torch.bfloat16),
+                                ("bf16_to_f32", torch.bfloat16, torch.float32)):
+        rows = torch.randn(n_img * N, D, device=dev).to(dt_in)
+        store = SimpleNamespace(rows=rows, starts=starts, counts=None, sample_shape=(N, D))
+        counted = SimpleNamespace(rows=rows, starts=starts, counts=torch.full((n_img,), N, dtype=torch.int32, device=dev), sample_shape=(N, D))
+        forms["gather_" + name] = lambda store=store, dt_out=dt_out: ops.gather_regions(store, idx, dt_out)
+        forms["gather_counts_" + name] = lambda store=counted, dt_out=dt_out: ops.gather_regions(store, idx, dt_out)
+        forms["unpack_" + name] = lambda x=rows[:B * N], dt_out=dt_out: ops.unpack_regions(x, lens, B, dt_out)
+    for fn in forms.values():
+        fn()
+    torch.cuda.synchronize()
+    return _alternate({k: (lambda fn=fn: 1e3 * _gpu_ms(fn, args.iters)) for k, fn in forms.items()}, args.blocks)
+
+
+def resident_main(args):
+    import numpy as np
+    assert torch.cuda.is_available(), "feed_bench.py --resident measures on a GPU"
+    dev = torch.device("cuda:0")
+    n_img, B, N, depth = args.store or 4096, args.batch, 36, args.depth
+    cfg = dict(n_img=n_img, N=N)
+    path = "/tmp/feed_bench_store_%dx%d.npy" % (n_img, N)
+    if not os.path.exists(path):
+        mm = np.lib.format.open_memmap(path, mode="w+", dtype=np.float32, shape=(n_img, N, D))
+        rs = np.random.RandomState(0)
+        for lo in range(0, n_img, 128):
+            mm[lo:lo + 128] = rs.standard_normal((min(128, n_img - lo), N, D)).astype(np.float32)
+        mm.flush()
+        del mm
+    store = feed.FeatureStore(path, workers=args.workers).populate()
+    rec = {"n_img": n_img, "B": B, "N": N, "steps": args.steps, "blocks": args.blocks, "upload": {}, "gather_us": {}}
+    resident = {}
+    for name, dt in (("f32", torch.float32), ("bf16", torch.bfloat16)):
+        resident[name] = feed.DeviceFeatureStore(store, dev, dtype=dt)
+        again = feed.DeviceFeatureStore(store, dev, dtype=dt)          # (the second upload: staging pages and file pages warm)
+        rec["upload"][name] = {"nbytes": again.nbytes, "first_s": round(resident[name].upload_seconds, 3), "second_s": round(again.upload_seconds, 3),
+                               "second_GBps": round(again.nbytes / again.upload_seconds / 1e9, 2)}
+        del again
+    rec["gather_us"]["B512xN36"] = _unpack_vs_gather_us(512, 36, 1024, args, dev)
+    rec["gather_us"]["B128xN100"] = _unpack_vs_gather_us(128, 100, 512, args, dev)
+    torch.cuda.empty_cache()
+    rs = np.random.RandomState(1)
+    qa = feed.qa_table(store, [{"v_idx": int(rs.randint(n_img)), "q_idxes": rs.standard_normal(2400).astype(np.float32), "q_id": i,
+                                "a_10_idx": [(int(c), 0.1) for c in rs.choice(NANS, 10, replace=False)]} for i in range(B * 8)],
+                         NANS, q_dtype=torch.float32)
+    forms, loaders = {}, []
+    ring = depth + 2 * args.producers + 2
+    feeds = [("resident_f32", dict(resident=resident["f32"]), "v_idx"), ("resident_bf16", dict(resident=resident["bf16"]), "v_idx"),
+             ("host_f32", dict(region_dtype=torch.float32), "v"), ("host_bf16", dict(region_dtype=torch.bfloat16), "v")]
+    for name, kw, key in feeds:
+        model = CoR2Model(["PAD"], NANS).to(dev).train().use_region_store(kw.get("resident"))
+        tr = DataParallelTrainer(model, graph=True, adopt_inputs=True, input_slots=depth)
+        loader = feed.store_batches(store, qa, B, NANS, shuffle=True, seed=0, pin=True, ring=ring, q_dtype=torch.float32,
+                                    prefetch=2 * args.producers, epochs=None, producers=args.producers, **kw)
+        loaders.append(loader)
+        for _ in range(ring):                               # every ring slot page-locked before anything is captured
+            next(loader)
+        pre = feed.DevicePrefetcher(iter(()), dev, depth=depth)
+
+        def run(n, tr=tr, pre=pre, loader=loader, key=key):
+            pre.it = (next(loader) for _ in range(n))
+            t0 = time.perf_counter()
+            for b in pre:
+                tr.step({key: b[key], "q_idxes": b["q_idxes"]}, b["a"])
+            torch.cuda.synchronize()
+            return B * n / (time.perf_counter() - t0)
+        run(4 + 2 * depth)                                  # warm-up + one graph per device slot
+        assert tr._graph is not None and len(tr._slots) == depth, "the fed step (%s) was not captured on every slot" % name
+        forms[name] = lambda run=run: run(args.steps)
+    # no feed at all: `depth` batches that are already on the device, in turn (what bench.py's step time stands for)
+    gen = torch.Generator().manual_seed(9)
+    rotating = [({"v": torch.randn(B, N, D, generator=gen).to(dev), "q_idxes": torch.randn(B, 2400, generator=gen).to(dev)},
+                 torch.softmax(torch.randn(B, NANS, generator=gen), 1).to(dev)) for _ in range(depth)]
+    tr = DataParallelTrainer(CoR2Model(["PAD"], NANS).to(dev).train(), graph=True, adopt_inputs=True, input_slots=depth)
+
+    def rotate(n, tr=tr):
+        t0 = time.perf_counter()
+        for i in range(n):
+            tr.step(*rotating[i % depth])
+        torch.cuda.synchronize()
+        return B * n / (time.perf_counter() - t0)
+    rotate(4 + 2 * depth)
+    assert tr._graph is not None and len(tr._slots) == depth, "the rotating step was not captured on every slot"
+    forms["rotating_on_device"] = lambda: rotate(args.steps)
+    rec["fed"] = _alternate({k: fn for k, fn in forms.items()}, args.blocks)
+    for name in rec["fed"]:
+        rec["fed"][name] = {k: (round(v) if not isinstance(v, list) else [round(x) for x in v]) for k, v in rec["fed"][name].items()}
+    for loader in loaders:
+        loader.close()
+    print(json.dumps(rec))
+
+
 def packed_child(args):
     assert torch.cuda.is_available(), "feed_bench.py --packed measures on a GPU"
     dev = torch.device("cuda:0")
@@ -232,6 +343,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--packed", action="store_true", help="packed (ragged) region batches against padded ones: see the module docstring")
+    ap.add_argument("--resident", action="store_true", help="the device-resident region store against the host feeds: see the module docstring")
     ap.add_argument("--counts", choices=["full", "uniform", "both"], default="both")
     ap.add_argument("--parent-tree", default=None)
     ap.add_argument("--blocks", type=int, default=4)
@@ -258,6 +370,8 @@ def main():
     args = ap.parse_args()
     if args.packed:
         return packed_main(args)
+    if args.resident:
+        return resident_main(args)
     if args.switch_interval > 0:
         sys.setswitchinterval(args.switch_interval)
     dev = torch.device("cuda:0")

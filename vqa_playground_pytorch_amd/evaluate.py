@@ -44,6 +44,7 @@ class Evaluator:
     @staticmethod
     def _model_keys(sample):
         v = "v_packed" if "v_packed" in sample else "v"              # packed region batches (feed.store_batches(packed=True))
+        v = "v_idx" if "v_idx" in sample else v                      # resident store: the images' indices (store_batches(resident=))
         keys = (v, "q_idxes") if "q_idxes" in sample else (v, "q")
         return keys + ("v_len",) if "v_len" in sample else keys      # per-sample region counts (cor2.Model.forward)
 
@@ -52,8 +53,16 @@ class Evaluator:
         'v_len' (region counts) is validated when it comes from the host and becomes the int32 device tensor the kernels read,
         so the replayed forward keeps it in a static input buffer like the rest.  A packed batch's 'v_packed' stands where 'v' does."""
         keys = list(self._model_keys(sample)) + [k for k in ("a", "a_mc_idx") if k in sample]
-        inputs = {k: sample[k].to(self.device, non_blocking=True) for k in keys if k != "v_len"}
-        if "v_len" in sample:
+        inputs = {k: sample[k].to(self.device, non_blocking=True) for k in keys if k not in ("v_len", "v_idx")}
+        if "v_idx" in sample:
+            # a resident-store batch: the indices, range-checked when they come from the host, as the int32 device tensor the
+            # gather reads -- a static input of the replayed forward like the rest; the counts are the store's
+            from . import ops
+            store = getattr(self.model, "region_store", None)
+            if store is None:
+                raise ValueError("'v_idx' needs a resident region store: attach one with model.use_region_store(...)")
+            inputs["v_idx"] = ops.image_indices(sample["v_idx"], len(store), self.device)
+        if "v_len" in sample and "v_idx" not in sample:
             from . import ops
             v = sample["v_packed"] if "v_packed" in sample else sample["v"]     # (packed: N rows for every entry of 'v_len')
             b = sample["v_len"].size(0) if "v_packed" in sample else v.size(0)

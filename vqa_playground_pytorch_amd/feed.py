@@ -72,12 +72,21 @@ def collate(items, num_ans, pin=False, answers="dense", packed=False, regions=No
     batch's largest pair count, shorter rows padded with -1 / 0 (ops.densify defines the format; the trainer takes the two keys).
     packed=True: a packed region batch -- 'v_packed' [B*N, D] (the items' real rows back to back in a capacity-sized buffer, the
     rest left unwritten) and 'v_len' instead of 'v'.  The items carry ragged 'v' [n_i, D] (then `regions` = N is given), or padded
-    'v' [N, D] plus 'v_len' (N from the shape unless given)."""
+    'v' [N, D] plus 'v_len' (N from the shape unless given).
+    Items for a device-resident store (DeviceFeatureStore) carry 'v_idx', their image's index, and no 'v': the batch then holds
+    'v_idx' int32 [B] and no region tensor (this is the one place that key needs a case of its own: it stands where 'v' is built)."""
     sparse = _check_answers(answers)
     B = len(items)
-    v0 = torch.as_tensor(items[0]["v"])
+    resident = "v" not in items[0] and "v_idx" in items[0]
+    if resident and packed:
+        raise ValueError("collate: items with 'v_idx' and no 'v' name rows of a resident store; packed=True does not apply")
+    v0 = torch.as_tensor(items[0]["v"]) if not resident else None
     mk = (lambda *s, dtype: torch.empty(*s, dtype=dtype).pin_memory()) if pin else (lambda *s, dtype: torch.empty(*s, dtype=dtype))
-    if packed:
+    if resident:
+        regions_part = {"v_idx": mk(B, dtype=torch.int32)}
+        for i, it in enumerate(items):
+            regions_part["v_idx"][i] = int(it["v_idx"])
+    elif packed:
         if regions is None and "v_len" not in items[0]:
             raise ValueError("collate(packed=True): ragged items need regions= (the capacity N per sample)")
         N = int(v0.shape[0] if regions is None else regions)
@@ -123,13 +132,13 @@ def collate(items, num_ans, pin=False, answers="dense", packed=False, regions=No
             batch["v_packed"][off:off + n].copy_(v[:n])
             batch["v_len"][i] = n
             off += n
-    elif "v_len" in items[0]:
+    elif "v_len" in items[0] and not resident:
         # per-item region counts (adaptive features padded to the store's N): int32 [B], what cor2.Model reads as sample['v_len']
         batch["v_len"] = mk(B, dtype=torch.int32)
         for i, it in enumerate(items):
             batch["v_len"][i] = _check_count(int(it["v_len"]), v0.shape[0], "item %d" % i)
     for i, it in enumerate(items):
-        if not packed:
+        if not packed and not resident:
             batch["v"][i].copy_(torch.as_tensor(it["v"], dtype=torch.float32))
         batch["q_idxes"][i].copy_(torch.as_tensor(it["q_idxes"], dtype=torch.long))
         if has_a:
@@ -145,7 +154,8 @@ def shard(batch, rank, world):
     ('v_packed' + 'v_len'): the rank's samples start at row off[r*B/P] of the global buffer (off = the exclusive prefix sum of
     'v_len') and its 'v_packed' is the view of (B/P)*N rows from there -- a capacity again, of which the rank's own sum of counts
     is meaningful; it cannot run past the global buffer, since off[b] <= b*N.  (DataParallelTrainer.shard is per tensor and
-    cannot do this: packed batches are sharded here.)"""
+    cannot do this: packed batches are sharded here.)  'v_idx' of a resident-store batch is a dim-0 tensor like 'q_idxes' and is
+    sliced like it: no case of its own."""
     _check_packed_keys(batch)
     if world == 1:
         return batch
@@ -166,7 +176,8 @@ class DevicePrefetcher:
     """Iterates device-resident batches; the H2D copies of the next batch overlap the consumer's work on the current
     one.  ``depth`` staging slots are allocated once in pinned host memory and once on the device (no per-batch
     allocation), copies run on a dedicated stream, and each yielded batch is handed to the consumer's stream with an
-    event wait -- the consumer never blocks the host."""
+    event wait -- the consumer never blocks the host.  A resident-store batch ('v_idx' int32 [B] instead of region rows,
+    store_batches(resident=)) needs no case here: the key is staged and copied like 'q_idxes', 4 bytes per sample."""
 
     def __init__(self, batches, device, depth=2):
         self.it = iter(batches)
@@ -462,6 +473,139 @@ class FeatureStore:
         return R
 
 
+def _check_store_layout(what, starts, counts, regions, total_rows):
+    """The invariant vqa_gather_regions relies on, for every image: 0 <= starts[i], counts[i] in 1..N (N without counts) and
+    starts[i] + counts[i] <= total_rows.  ValueError naming the first image that breaks it."""
+    starts = np.asarray(starts, dtype=np.int64)
+    c = np.asarray(counts, dtype=np.int64) if counts is not None else np.full(starts.shape, int(regions), np.int64)
+    if starts.ndim != 1 or c.shape != starts.shape or starts.size < 1:
+        raise ValueError("%s: starts %s and counts %s must be [n_img], n_img >= 1" % (what, starts.shape, c.shape))
+    bad = (c < 1) | (c > regions)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError("%s: image %d has region count %d outside 1..%d" % (what, i, int(c[i]), regions))
+    bad = (starts < 0) | (starts + c > total_rows)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError("%s: image %d owns rows %d..%d, the store holds %d" % (what, i, int(starts[i]), int(starts[i] + c[i]), total_rows))
+
+
+def _free_bytes(device):
+    """bytes the device can still hand out: HIP's figure for a GPU (memory torch has cached but not in use is not counted), the
+    available physical memory for the CPU"""
+    if device.type == "cuda":
+        return int(torch.cuda.mem_get_info(device)[0])
+    try:
+        return int(os.sysconf("SC_AVPHYS_PAGES")) * int(os.sysconf("SC_PAGE_SIZE"))
+    except (ValueError, OSError, AttributeError):
+        return 1 << 62
+
+
+class DeviceFeatureStore:
+    """A FeatureStore uploaded ONCE into device memory: a batch then names its images ('v_idx' int32 [B], 2 KB at B = 512) and the
+    device gathers their rows out of HBM (ops.gather_regions, csrc/region_gather.hip) -- no host gather, no pinned region slots,
+    no host -> device copy of region rows in the step.  The reference's feature file for VQA v2 train+val is 36.4 GB as fp32 and
+    18.2 GB as bf16 (123 287 x 36 x 2048); an MI355X has 288 GB.
+
+    store: a FeatureStore of any form -- padded, padded with counts=, or ragged (offsets=).  dtype: float32, or bfloat16 -- then
+    the rows are rounded on the way up, by store.gather / store.gather_packed, i.e. the round-to-nearest-even of the bf16
+    transport (store_batches(region_dtype=torch.bfloat16)): an fp32 model widens them in the gather, exactly.  fp32 rows are never
+    narrowed on the device.  compact=True: a padded store that has counts is uploaded as its real rows only, back to back (the
+    ragged layout); compact=False keeps its padded layout.  The upload runs in chunks through ONE pinned staging buffer of
+    chunk_bytes (two halves: the host gather of one chunk overlaps the copy of the other); there is never a second full copy in
+    host memory.
+
+    Fields: rows [total_rows, D] (dtype), starts int64 [n_img] (the first row of image i), counts int32 [n_img] or None (every
+    image has N rows) -- tensors on `device`; sample_shape (N, D), len() = n_img, nbytes (the three tensors), upload_seconds;
+    index(img_filename) / name_to_idx / idx_to_name are the host store's.  device="cpu" keeps the tensors on the host: the same
+    class for host tests and gloo runs.
+
+    Checked once, on the host, before anything is uploaded (ValueError): 0 <= starts[i], every count in 1..N and
+    starts[i] + counts[i] <= total_rows -- for the host store's layout and for the one built here.  The gather kernel clamps the
+    index and the count it reads and relies on this for the rest.  Capacity: construction raises ValueError naming both numbers
+    when nbytes exceeds the device's free memory minus reserve_bytes -- what is kept free for the model, its activations and
+    the captured graphs' pools.  reserve_bytes defaults to 8 GiB on a GPU and to 0 on the CPU."""
+
+    DEFAULT_RESERVE_BYTES = 8 << 30
+
+    def __init__(self, store, device, dtype=torch.float32, compact=True, chunk_bytes=256 << 20, reserve_bytes=None):
+        self.device = torch.device(device)
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("DeviceFeatureStore: dtype must be float32 or bfloat16, got %s" % (dtype,))
+        N, D = (int(x) for x in store.sample_shape)
+        n_img = len(store)
+        self.sample_shape, self._n_img, self.dtype = (N, D), n_img, dtype
+        self.name_to_idx, self.idx_to_name = store.name_to_idx, getattr(store, "idx_to_name", None)
+        # the host store's own layout, as its gathers will read it
+        src_rows = int(store.features.shape[0]) * (1 if store.ragged else N)
+        src_starts = store._starts if store.ragged else np.arange(n_img, dtype=np.int64) * N
+        _check_store_layout("DeviceFeatureStore: the host store", src_starts, store.counts, N, src_rows)
+        self.packed_upload = store.counts is not None and (store.ragged or bool(compact))
+        if self.packed_upload:
+            c64 = store.counts.astype(np.int64)
+            starts = np.cumsum(c64) - c64
+            total_rows = int(c64.sum())
+        else:
+            starts, total_rows = src_starts, n_img * N
+        counts = store.counts
+        _check_store_layout("DeviceFeatureStore", starts, counts, N, total_rows)
+        item = torch.empty((), dtype=dtype).element_size()
+        self.nbytes = total_rows * D * item + n_img * 8 + (n_img * 4 if counts is not None else 0)
+        reserve = (self.DEFAULT_RESERVE_BYTES if self.device.type == "cuda" else 0) if reserve_bytes is None else int(reserve_bytes)
+        free = _free_bytes(self.device)
+        if self.nbytes > free - reserve:
+            raise ValueError("DeviceFeatureStore: the store needs %d bytes, %s has %d free minus %d reserved = %d"
+                             % (self.nbytes, self.device, free, reserve, free - reserve))
+        import time
+        t0 = time.perf_counter()
+        self.rows = torch.empty(total_rows, D, dtype=dtype, device=self.device)
+        self.starts = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.int64)).to(self.device)
+        self.counts = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.int32)).to(self.device) if counts is not None else None
+        self._upload(store, starts, max(int(chunk_bytes), 2 * N * D * item))
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        self.upload_seconds = time.perf_counter() - t0
+
+    def _upload(self, store, starts, chunk_bytes):
+        N, D = self.sample_shape
+        n_img, cuda = self._n_img, self.device.type == "cuda"
+        half_rows = chunk_bytes // 2 // (D * self.rows.element_size())          # (>= N: one image always fits a half)
+        stage = torch.empty(2, half_rows, D, dtype=self.dtype)
+        if cuda:
+            stage = stage.pin_memory()
+        lens = torch.empty(half_rows, dtype=torch.int32) if self.packed_upload else None
+        done = [None, None]
+        end = np.append(starts[1:], self.rows.size(0)) if self.packed_upload else None      # image i's rows end at end[i]
+        lo = k = 0
+        while lo < n_img:
+            if self.packed_upload:
+                hi = max(lo + 1, int(np.searchsorted(end, starts[lo] + half_rows, side="right")))
+            else:
+                hi = min(n_img, lo + half_rows // N)
+            half = stage[k % 2]
+            if done[k % 2] is not None:
+                done[k % 2].synchronize()                # the copy that last read this half has finished
+            ids = np.arange(lo, hi, dtype=np.int64)
+            if self.packed_upload:
+                r = store.gather_packed(ids, half, lens)
+                r0 = int(starts[lo])
+            else:
+                store.gather(ids, half[:(hi - lo) * N].view(hi - lo, N, D))
+                r, r0 = (hi - lo) * N, lo * N
+            self.rows[r0:r0 + r].copy_(half[:r], non_blocking=cuda)
+            if cuda:
+                done[k % 2] = torch.cuda.Event()
+                done[k % 2].record()
+            lo, k = hi, k + 1
+
+    def __len__(self):
+        return self._n_img
+
+    def index(self, img_filename):
+        """FeatureStore.index: the row of an image file name (KeyError for an unknown image)."""
+        return self.name_to_idx[img_filename]
+
+
 class _QaTable:
     """The per-question records turned into arrays ONCE (the reference keeps dicts and pays Python per sample per epoch in its
     DataLoader workers): feature rows, the question matrix, ids, and the soft answers as CSR (datasets.py:963-969: a[c_id] = c_prob,
@@ -550,7 +694,7 @@ def _sorted_by_question_length(ids, q, shards):
 
 def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, pin=True, region_dtype=torch.float32, ring=3,
                   q_dtype=torch.long, prefetch=0, epochs=1, producers=1, answers="dense", packed=False, sort_questions=False,
-                  shards=1):
+                  shards=1, resident=None):
     """The reference's loader (datasets.py:893-977: `Inner.__getitem__` + DataLoader(batch_size, shuffle, pin_memory=True), no
     drop_last) over a FeatureStore: yields batch dicts {'v' [B,N,D], 'q_idxes' [B,T], 'q_id' [B], 'a' [B,num_ans]} of host tensors.
     qa_items: the reference's per-question records -- 'img_filename' (or 'v_idx'), 'q_idxes', 'q_id', 'a_10_idx' [(answer id,
@@ -577,13 +721,24 @@ def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, p
     non-zero tokens) BEFORE anything is gathered -- a stable sort, so every key of the batch follows, packed rows included -- for
     the length-aware question encoder, whose products skip row tiles that hold no unfinished question (SkipThoughts(length_aware=
     True)).  shards=P: the sort happens inside each of the P contiguous B/P slices that `shard` hands to a rank, so ranks keep equal
-    work.  Which records make up a batch does not change, and order inside a batch does not change the training sum."""
+    work.  Which records make up a batch does not change, and order inside a batch does not change the training sum.
+    resident=DeviceFeatureStore: the region rows already live on the device, so the batches carry 'v_idx' int32 [B] -- the image
+    of each sample, from the same staging ring -- instead of 'v' / 'v_packed' / 'v_len': no region staging tensor is allocated and
+    no gather runs here; the model the store is attached to (RegionQuestionModel.use_region_store) gathers on the device and takes
+    the counts from the store.  Everything else (sort_questions, shards, answers, prefetch, producers) works as above; `store` may
+    be the host store the resident one was built from, or the resident store itself.  With packed=True or a region_dtype other
+    than float32 it raises ValueError: how the rows are laid out and stored was decided when the store was uploaded."""
     sparse = _check_answers(answers)
     if int(shards) < 1:
         raise ValueError("store_batches: shards must be >= 1, got %r" % (shards,))
+    if resident is not None:
+        if packed or region_dtype != torch.float32:
+            raise ValueError("store_batches(resident=): no region rows are shipped, so packed=True / region_dtype= do not apply "
+                             "(the resident store's layout and dtype were chosen when it was uploaded)")
+        store = resident
     if packed and store.counts is None:
         raise ValueError("store_batches(packed=True) needs a store with region counts (FeatureStore(counts=) or (offsets=, regions=))")
-    if not packed and getattr(store, "ragged", False):
+    if resident is None and not packed and getattr(store, "ragged", False):
         raise ValueError("store_batches: a ragged store (offsets=) serves packed batches only: pass packed=True")
     n = len(qa_items.rows) if isinstance(qa_items, _QaTable) else len(qa_items)
 
@@ -594,6 +749,8 @@ def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, p
         return o
     table = qa_items if isinstance(qa_items, _QaTable) else _QaTable(store, qa_items, num_ans, q_dtype)
     T = table.q.shape[1]
+    if resident is not None and n and (table.rows.min() < 0 or table.rows.max() >= len(resident)):
+        raise IndexError("store_batches(resident=): feature index out of range [0, %d)" % len(resident))
     if sort_questions and table.q.dtype.kind not in "iu":
         raise ValueError("store_batches(sort_questions=True) sorts by the count of non-zero token ids: it needs q_dtype=torch.long")
     has_a = table.kind is not None
@@ -612,20 +769,25 @@ def store_batches(store, qa_items, batch_size, num_ans, shuffle=False, seed=0, p
         with slot_lock:
             while len(slots) <= k:
                 v_shape = (batch_size * store.sample_shape[0], store.sample_shape[1]) if packed else (batch_size, *store.sample_shape)
-                slots.append({"v": mk(*v_shape, dtype=region_dtype), "q_idxes": mk(batch_size, T, dtype=q_dtype),
+                slots.append({"v": mk(*v_shape, dtype=region_dtype) if resident is None else None,
+                              "v_idx": mk(batch_size, dtype=torch.int32) if resident is not None else None,
+                              "q_idxes": mk(batch_size, T, dtype=q_dtype),
                               "a": mk(batch_size, num_ans, dtype=torch.float32) if has_a and not sparse else None,
                               "a_idx": mk(batch_size, K, dtype=torch.int32) if K else None,
                               "a_val": mk(batch_size, K, dtype=torch.float32) if K else None,
-                              "v_len": mk(batch_size, dtype=torch.int32) if store.counts is not None else None})
+                              "v_len": mk(batch_size, dtype=torch.int32) if store.counts is not None and resident is None else None})
         s = slots[k]
-        if packed:
+        if resident is not None:
+            batch = {"v_idx": s["v_idx"][:b]}
+            batch["v_idx"].numpy()[...] = table.rows[ids]
+        elif packed:
             store.gather_packed(table.rows[ids], s["v"], s["v_len"])
             batch = {"v_packed": s["v"][:b * store.sample_shape[0]], "v_len": s["v_len"][:b]}
         else:
             batch = {"v": store.gather(table.rows[ids], s["v"])}
         batch.update({"q_idxes": s["q_idxes"][:b], "q_id": torch.from_numpy(table.q_ids[ids])})
         batch["q_idxes"].numpy()[...] = table.q[ids]
-        if store.counts is not None and not packed:
+        if store.counts is not None and not packed and resident is None:
             batch["v_len"] = s["v_len"][:b]
             batch["v_len"].numpy()[...] = store.counts[table.rows[ids]]
         if K:

@@ -539,7 +539,11 @@ class RegionQuestionModel(nn.Module):
         A packed batch carries 'v_packed' [B*N, 2048] (fp32 or bf16: the capacity-sized buffer whose first sum(v_len) rows are the
         samples' real rows back to back) and the then mandatory 'v_len' instead of 'v': ops.unpack_regions rebuilds the padded
         tensor, exact zeros on the padding, in one pass -- bf16 rows into an fp32 model widened by that same pass, fp32 rows into
-        a bf16 model unpacked as fp32 and cast where a padded fp32 'v' is."""
+        a bf16 model unpacked as fp32 and cast where a padded fp32 'v' is.
+        A resident-store batch carries 'v_idx' int [B], the image of each sample, and no region rows at all: ops.gather_regions
+        reads them out of the store attached with use_region_store, and v_len comes from the store when it has counts."""
+        if "v_idx" in sample:
+            return self._resident_region_input(sample, counts)
         if "v_packed" in sample:
             return self._packed_region_input(sample, counts)
         v = sample["v"]
@@ -554,6 +558,36 @@ class RegionQuestionModel(nn.Module):
         if v.is_cuda and v.dtype == torch.bfloat16 and self.compute_dtype == torch.float32:
             v = ops.widen_bf16(v)
         return v, v_len
+
+    region_store = None                 # the attached feed.DeviceFeatureStore (use_region_store): a plain attribute
+
+    def use_region_store(self, dstore):
+        """Attach (or, with None, detach) a device-resident region store (feed.DeviceFeatureStore): batches may then carry 'v_idx'
+        instead of 'v' / 'v_packed' / 'v_len'.  The store is a plain attribute -- no module, buffer or parameter: state_dict(),
+        parameters() and .to() do not see it.  A batch without 'v_idx' runs exactly as without a store.  -> self."""
+        if dstore is not None:
+            N, D = dstore.sample_shape
+            regions = getattr(self, "regions", None)
+            if D != 2048 or (regions is not None and N != regions):
+                raise ValueError("region store of %d x %d rows per image does not fit this model (%s regions of 2048)"
+                                 % (N, D, regions if regions is not None else "any number of"))
+        object.__setattr__(self, "region_store", dstore)
+        return self
+
+    def _resident_region_input(self, sample, counts):
+        """'v_idx' -> (v, v_len) out of the attached store.  bf16 rows into an fp32 model are widened in the gather, bf16 rows
+        into a bf16 model copied, fp32 rows gathered as fp32 (and cast by the model where a padded fp32 'v' is)."""
+        clash = [k for k in ("v", "v_packed", "v_len") if k in sample]
+        if clash:
+            raise ValueError("a batch names its images ('v_idx') or carries their rows and counts (%s), not both"
+                             % ", ".join(repr(k) for k in clash))
+        store = self.region_store
+        if store is None:
+            raise ValueError("'v_idx' needs a resident region store: attach one with model.use_region_store(DeviceFeatureStore(...))")
+        if store.counts is not None and not counts:
+            raise ValueError("this model reads no per-sample region counts and so takes no resident store that has them")
+        widen = store.rows.dtype == torch.bfloat16 and self.compute_dtype == torch.float32
+        return ops.gather_regions(store, sample["v_idx"], torch.float32 if widen else store.rows.dtype, want_len=counts)
 
     def _packed_region_input(self, sample, counts):
         if "v" in sample:

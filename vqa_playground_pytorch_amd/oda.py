@@ -65,7 +65,9 @@ class Model(RegionQuestionModel):
         return [p for m in (self.fusion_final, self.linear_classif) for p in m.parameters()]
 
     def forward(self, sample, _cut=None):
-        if ("v_len" in sample or "v_packed" in sample) and not self.region_counts:      # (a packed batch is one with counts)
+        resident_counts = "v_idx" in sample and self.region_store is not None and self.region_store.counts is not None
+        if ("v_len" in sample or "v_packed" in sample or resident_counts) and not self.region_counts:
+            # (a packed batch is one with counts; so is a 'v_idx' batch whose resident store has them)
             # the attention weights of this model are indexed by region slot (fuse_dim = regions * 310): masking them changes
             # which samples train which slot, so the model reads the counts only when it was built to
             raise ValueError("ODA.Model takes no per-sample region counts: drop 'v_len' from the sample, or build the model "

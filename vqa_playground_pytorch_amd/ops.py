@@ -596,6 +596,63 @@ def unpack_regions(v_packed, v_len, batch, out_dtype=None):
     return out
 
 
+def image_indices(idx, n_img, device):
+    """A sample's 'v_idx' entry -> the int32 [B] tensor on `device` that vqa_gather_regions reads, as region_counts does for
+    'v_len'.  A host tensor (the feed's) is range-checked here: every index must lie in [0, n_img), else IndexError.  A device
+    tensor is taken as is -- no sync in the step; the kernel clamps what it reads.  int64 is accepted and converted."""
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 1 or idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError("v_idx must be an int32 or int64 tensor [B] of image indices")
+    if not idx.is_cuda and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n_img):
+        raise IndexError("v_idx holds %d..%d: every image index must lie in [0, %d)" % (int(idx.min()), int(idx.max()), n_img))
+    return idx.to(device=device, dtype=torch.int32, non_blocking=True).contiguous()
+
+
+def gather_regions(dstore, idx, out_dtype=None, want_len=True):
+    """A batch of image indices -> (v [B, N, D], v_len) out of a device-resident store (csrc/region_gather.hip, one launch).
+    dstore: a feed.DeviceFeatureStore (or anything with its fields) -- rows [total_rows, D] fp32 or bf16, starts int64 [n_img],
+    counts int32 [n_img] or None, sample_shape (N, D).  idx: int32 / int64 [B], see image_indices.  With i = clamp(idx[b], 0,
+    n_img - 1) and c = clamp(counts[i], 0, N) (N without counts): v[b, r] = rows[starts[i] + r] for r < c, exact +0.0 behind.
+    v_len: int32 [B] = c, written by the same launch, when the store has counts and want_len; else None.  out_dtype: the rows'
+    (default), or float32 for bf16 rows -- widened exactly, the bits of widen_bf16; float32 rows are never narrowed here.  No
+    autograd: region features are inputs.  CPU tensors run the same definition in torch (the semantics, for tests, hosts without a
+    GPU and gloo runs)."""
+    rows, starts, counts = dstore.rows, dstore.starts, dstore.counts
+    N, D = (int(x) for x in dstore.sample_shape)
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.size(1) != D or rows.dtype not in _REGION_DTYPES:
+        raise ValueError("gather_regions: the store's rows must be a float32 or bfloat16 tensor [total_rows, %d]" % D)
+    out_dtype = rows.dtype if out_dtype is None else out_dtype
+    if (rows.dtype, out_dtype) not in ((torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16),
+                                       (torch.bfloat16, torch.float32)):
+        raise ValueError("gather_regions: %s rows into %s (float32 rows are cast by the model, not here)" % (rows.dtype, out_dtype))
+    n_img = starts.numel()
+    if starts.dtype != torch.int64 or starts.dim() != 1 or n_img < 1 or starts.device != rows.device:
+        raise ValueError("gather_regions: the store's starts must be int64 [n_img] on %s" % rows.device)
+    if counts is not None and (counts.dtype != torch.int32 or counts.shape != (n_img,) or counts.device != rows.device):
+        raise ValueError("gather_regions: the store's counts must be int32 [n_img] = [%d] on %s" % (n_img, rows.device))
+    idx = image_indices(idx, n_img, rows.device)
+    B = idx.numel()
+    if B < 1:
+        raise ValueError("gather_regions: an empty batch")
+    want_len = bool(want_len) and counts is not None
+    if not rows.is_cuda:
+        i = idx.long().clamp(0, n_img - 1)
+        c = counts[i].clamp(0, N).long() if counts is not None else torch.full((B,), N, dtype=torch.long)
+        r = torch.arange(N)
+        real = r[None, :] < c[:, None]
+        src = torch.where(real, starts[i][:, None] + r[None, :], torch.zeros((), dtype=torch.long))
+        out = rows[src.reshape(-1)].to(out_dtype).view(B, N, D)
+        out = torch.where(real[:, :, None], out, torch.zeros((), dtype=out_dtype))
+        return out, (c.to(torch.int32) if want_len else None)
+    if idx.data_ptr() % 16:
+        idx = idx.clone()               # (a slice of a larger batch's indices: the kernel wants its pointers 16-byte aligned)
+    out = torch.empty(B, N, D, device=rows.device, dtype=out_dtype)
+    v_len = torch.empty(B, device=rows.device, dtype=torch.int32) if want_len else None
+    _launch("gather_regions", (B, N, D, rows.dtype == torch.bfloat16, out_dtype == torch.bfloat16),
+            _lib.lib().vqa_gather_regions, _p(rows), rows.size(0), _p(starts), _p(counts), n_img, _p(idx), _p(out), _p(v_len),
+            B, N, D, int(rows.dtype == torch.bfloat16), int(out_dtype == torch.bfloat16))
+    return out, v_len
+
+
 def pack_bf16(src, dst, batch_stride, row_stride, col_stride, zero_fill=True, offset=0):
     """fp32 [batch, rows, cols] (or [rows, cols]) -> bf16 scattered into ``dst`` (from element ``offset`` on) with the
     given element strides; with zero_fill that part of ``dst`` is zeroed first (the pads of the padded / transposed

@@ -442,6 +442,7 @@ class DataParallelTrainer:
         """The entries of a sample dict the models read (config/CoR2.py:203-205): feeder batches also carry the target
         'a' and 'q_id', which must not be cloned / re-copied into the graph's input buffers every step."""
         v = "v_packed" if "v_packed" in sample else "v"              # packed region batches (feed.store_batches(packed=True))
+        v = "v_idx" if "v_idx" in sample else v                      # resident store: the images' indices (store_batches(resident=))
         keys = {v, "q_idxes"} if "q_idxes" in sample else {v, "q"}
         return keys | {"v_len"} if "v_len" in sample else keys       # per-sample region counts (cor2.Model.forward)
 
@@ -464,7 +465,7 @@ class DataParallelTrainer:
         which KLD and BCE are computed directly and CE draws its label per row and step (``last_labels``)."""
         if isinstance(target, dict):
             target = SparseTarget(target["a_idx"], target["a_val"])
-        v = sample.get("v_packed", sample.get("v"))
+        v = sample.get("v_packed", sample.get("v"))     # (None for a resident-store batch: 'v_idx', whose counts the store holds)
         if self.hip and sample.get("v_len") is not None and v is not None and v.is_cuda:
             # per-sample region counts: validated (a host tensor) and brought to the int32 device form once, so that the graph
             # path can keep them in a static input buffer like 'v' and 'q_idxes'.  N of a packed batch is its capacity's:
@@ -738,10 +739,10 @@ class DataParallelTrainer:
                 k not in sample or sample[k].shape != t.shape or sample[k].dtype != t.dtype for k, t in g["sample"].items()) or \
                 ("v_len" in sample) != ("v_len" in g["sample"]):
             # a batch of another shape (the last one of an epoch), a batch with region counts after a capture without them (the
-            # graph holds the unmasked kernels) or the other way round, a packed batch ('v_packed') after a capture on padded ones
-            # or the other way round (one of the captured keys is missing), or the model switched between train() and eval() since
-            # the capture (dropout is baked into the graph): this step is launched kernel by kernel; the captured graphs
-            # stay valid for the regular steps that follow
+            # graph holds the unmasked kernels) or the other way round, a packed batch ('v_packed') or a resident-store batch
+            # ('v_idx') after a capture on padded ones or the other way round (one of the captured keys is missing), or the model
+            # switched between train() and eval() since the capture (dropout is baked into the graph): this step is launched
+            # kernel by kernel; the captured graphs stay valid for the regular steps that follow
             return self.step_eager(sample, target)
         slot = self._slot_of(sample, target)
         if slot is None and len(self._slots) < self.input_slots:
